@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the GDB-NeRF hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2] [--precision f32|f16|f32x] [--path fused|unfused]
+    python bench.py --gpus N --steps K --warmup W [--workload c2] [--precision f32|f16|f32x] [--path fused|unfused] [--dump-outputs DIR]
 
 One *step* = one pass of the hot path (per-frame preparation: camera block + feature mip pyramid; then
 build_rays → sample → encode → MLP → composite) over one synthetic frame of the workload, inputs already
@@ -25,7 +25,9 @@ N > 1 (launched by torch.distributed.run, one rank per GPU), both modes timed in
   frames (the `independent_frames` record, weak scaling): every rank renders its own frame (independent target views, as an
          evaluation sweep does), no data-path collective; `--shard frames` makes it the headline.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR: what the headline's timed path returned in its last step (bundle_feat,
+bundle_depth, bundle_opacity; N > 1 rows mode: the gathered frame) as DIR/<name>.npy, float32; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -94,6 +96,27 @@ def kernel_source_sha16():
 
 def to_dev(frame, dev):
     return {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in frame.items()}
+
+
+# --dump-outputs: 64 MB in all, the .npy headers included
+DUMP_DATA_BYTES = 60 << 20
+
+
+def dump_outputs(dir_, arrays):
+    """Write {name: tensor} as dir_/<name>.npy in float32 and return the record for the JSON line.  Above DUMP_DATA_BYTES in all,
+    every array keeps the same share of its rows, drawn by numpy's default_rng(0) (arrays with as many rows keep the same rows)."""
+    os.makedirs(dir_, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    frac = min(1.0, DUMP_DATA_BYTES / total) if total else 1.0
+    rec = {"dir": dir_, "dtype": "float32", "row_sample": "all rows" if frac == 1.0 else "default_rng(0), sorted", "arrays": {}}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        n = a.shape[0]
+        if frac < 1.0:
+            a = a[np.sort(np.random.default_rng(0).choice(n, size=int(n * frac), replace=False))]
+        np.save(os.path.join(dir_, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        rec["arrays"][name] = {"shape": list(a.shape), "rows_of": n}
+    return rec
 
 
 def fine_rgb(bf, H, W):
@@ -409,7 +432,12 @@ def main():
     ap.add_argument("--streams", type=int, default=1,
                     help="fused path, N = 1 only: render consecutive (independent) frames on this many HIP streams with their own "
                          "workspaces, so one frame's fill/drain overlaps the next; per-launch durations then overlap too (default 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (bundle_feat, bundle_depth, "
+                         "bundle_opacity) as DIR/<name>.npy in float32; above 64 MB a fixed, seeded sample of bundle rows (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver's N = 1 command form has it: start the N ranks ourselves.  This process has
@@ -490,6 +518,7 @@ def main():
     eng, out, _ = lanes[0]
     nb = eng.n_bundles
     counter = [0]
+    unfused_out = [None]  # (bundle_feat, depth, opacity) of the unfused path's last step
 
     def events():
         return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -522,7 +551,16 @@ def main():
             sigma, feat = eng.mlp(vox, rfd, s["total"])
             if sample:
                 e1.record(); pairs.append((e0, e1))
-            eng.composite(sigma, feat, s["z_vals"], s["indices"], nb, s["total"])
+            unfused_out[0] = eng.composite(sigma, feat, s["z_vals"], s["indices"], nb, s["total"])[1:]
+
+    def step_outputs():
+        """Device copies of what the last step_frame returned to its caller (read after the synchronise that ends a timed region)."""
+        if args.path == "unfused":
+            o = unfused_out[0]
+        else:
+            o = lanes[(counter[0] - 1) % len(lanes)][1] if args.streams > 1 else out
+        return dict(zip(("bundle_feat", "bundle_depth", "bundle_opacity"), (t.clone() for t in o)))
+    last = {}  # the headline's timed path, its last step: name -> device tensor
 
     # The render's GPU time on HBM-cold inputs: one engine (= one workspace: camera block, pyramid, plan) per ring copy of the frame, each
     # prepared ONCE on its copy, then n render calls cycling through them between one HIP event pair - the kernel the timed region runs,
@@ -549,10 +587,11 @@ def main():
         return ms
 
     # ---- N > 1, rows mode: one frame, row strips, packed output, one all-gather --------------------------------------
-    def rows_record(wl_name, wl_, frame_np_, steps, warmup, eng_=None, pname_=None):
+    def rows_record(wl_name, wl_, frame_np_, steps, warmup, eng_=None, pname_=None, keep=None):
         """north_star's partitioning of ONE frame of workload `wl_name` over the ranks: contiguous bundle-map row strips; every rank
         prepares (whole pyramid, strip-only plan), renders its strip straight into the packed buffer and ONE all-gather leaves all rows
-        on every rank.  Returns the record (rank-0 view + every rank's prepare / kernel / all-gather times)."""
+        on every rank.  Returns the record (rank-0 view + every rank's prepare / kernel / all-gather times); `keep` (a dict) receives
+        the gathered outputs of the last timed step."""
         Ho_, Wo_ = wl_["Ho"], wl_["Wo"]
         H_, W_ = Ho_ // 2, Wo_ // 2
         fr = to_dev(frame_np_, dev)
@@ -586,6 +625,8 @@ def main():
                 a1.record(); ap_.append((a0, a1))
         timed.rewarm(step, min(args.prewarm_ms, 150.0))
         dt_ = timed.run(step, warmup, steps)
+        if keep is not None:  # the packed rows [bundle_feat | depth | opacity]
+            keep.update(bundle_feat=g.full[:, :e.Q].clone(), bundle_depth=g.full[:, e.Q].clone(), bundle_opacity=g.full[:, e.Q + 1].clone())
         timed.sample(step)
         # untimed check: the gathered strips equal this rank's own render of the whole frame, bit for bit
         e.prepare(rg[ri[0]])
@@ -619,6 +660,8 @@ def main():
     r0, r1 = 0, H
     if world == 1:
         dt = timed.run(step_frame, args.warmup, args.steps)
+        if args.dump_outputs:
+            last.update(step_outputs())
         if args.path == "fused" and args.streams == 1:
             kern_warm_ms = hot_ms(timed, lambda: eng.render(0, H, None, out))
             kern_fused_ms = ring_kernel_ms() if len(ring) > 1 else kern_warm_ms
@@ -628,12 +671,15 @@ def main():
         rays_per_step, share = Ho * Wo, 1.0
     else:
         # both modes are timed; --shard picks the headline
-        rec_rows, _, (r0, r1) = rows_record(args.workload, wl, frame_np, args.steps, args.warmup, eng)
+        rec_rows, _, (r0, r1) = rows_record(args.workload, wl, frame_np, args.steps, args.warmup, eng,
+                                            keep=last if args.dump_outputs and args.shard == "rows" else None)
         # frames mode: every rank its own frame (seeded by rank)
         frame = to_dev(synthetic.make_frame(Ho, Wo, V=V, scene=wl["scene"], seed=rank), dev)
         ring[:] = [frame] + [{k: v.clone() for k, v in frame.items()} for _ in range(nring - 1)]
         kern_pairs.clear()
         dt_frames = timed.run(step_frame, args.warmup, args.steps)
+        if args.dump_outputs and args.shard == "frames":
+            last.update(step_outputs())
         timed.sample(step_frame)
         kern_frames = ev_ms(kern_pairs)
         rec_frames = {"mode": "frames: every rank its own frame, no data-path collective", "scaling": "weak",
@@ -956,6 +1002,8 @@ def main():
     if rank == 0 and not args.no_cpu_baseline:
         # N > 1: the 8-thread row only, on rank 0, after the process group is gone (no rank waits on it)
         res["cpu_baseline"] = cpu_baseline(wl, frame_np, weights_np, quick=world > 1)
+    if rank == 0 and args.dump_outputs:
+        res["dumped_outputs"] = dump_outputs(args.dump_outputs, last)
     if rank == 0:
         print(json.dumps(res), flush=True)
 
