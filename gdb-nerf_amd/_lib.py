@@ -79,6 +79,12 @@ _SIGNATURES = {
     "gdb_pack_decoder_weights": (C.c_int, [_CFG, C.c_int32, C.POINTER(_P), _P]),
     "gdb_decoder_workspace_bytes": (C.c_int, [_CFG, _FRM, C.POINTER(C.c_size_t)]),
     "gdb_decode": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
+    "gdb_decoder_rows_workspace_bytes": (C.c_int, [_CFG, _FRM, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "gdb_decoder_rows_layout": (C.c_int, [_CFG, _FRM, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gdb_decode_rows": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
+    "gdb_merge_packed_rows": (C.c_int, [_CFG, _FRM, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "gdb_upsample_maps": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -216,14 +216,16 @@ extern "C" int gdb_pack_decoder_weights(const GdbConfig* cfg, int32_t num_layers
 // alternate whatever the number of blocks), Y = [x1 | x2] of the block in flight, T = conv3's output; the dense block's torch.cat([x, x1, x2]) is "chunks 0-1
 // from P[b], chunks 2-3 from Y".  part = per-(row, 32-pixel segment) channel sums of T (written by conv3's epilogue), part2 = their
 // sums per group of DEC_SEG segments, gate = the block's 64 gates per batch item, count = one arrival counter per batch item.
+// A row-window decode (gdb_decode_rows) sizes the activations to its window of Hw rows and keeps part / part2 frame-sized (Hf rows):
+// part receives the other ranks' rows before each squeeze-excitation.
 #ifndef DEC_SEG
 #define DEC_SEG 128   // segments per workgroup of k_se_gate's first stage (256x320, 2,560 segments: 16 / 32 / 64 / 128 / 256 -> 18.4 / 10.8 / 7.9 / 6.6 / 7.8 us: the last arriver's serial tail)
 #endif
 struct DecWs { size_t P[3], Y, T, part, part2, gate, count, X, U, total; int nseg, ngrp; };   // X, U: upscale_factor 4 only (the blocks' output with the last gate applied; the first up stage's (2H, 2W, 64) map)
-static DecWs dec_ws(int B, int H, int W, int bundle_size = 2) {
+static DecWs dec_ws(int B, int H, int W, int bundle_size = 2, int Hf = 0) {
     DecWs w{};
     const size_t n = (size_t)B * H * W;
-    w.nseg = H * ((W + 31) / 32);
+    w.nseg = (Hf > 0 ? Hf : H) * ((W + 31) / 32);
     w.ngrp = (w.nseg + DEC_SEG - 1) / DEC_SEG;
     size_t o = 0;
     for (int i = 0; i < 3; ++i) { w.P[i] = o; o = align_up(o + sizeof(float) * n * DEC_NF, 256); }
@@ -263,6 +265,10 @@ struct ConvArgs {
     float* se_part;                 // SEP kernels (conv3): channel sums of the output per (row, 32-pixel segment)
     unsigned* zero;                 // in_conv: the arrival counters of k_se_gate, cleared for this decode
     int B, H, W, tilesX, tilesY;
+    // row window (gdb_decode_rows): the map the kernel runs on is rows [wy0, wy0 + H) of a frame of Hf rows.  `in` holds in_H rows per
+    // batch item starting at row in_y0 (in_conv reads the frame-sized bundle rows in place; every other input is window-sized); se_part
+    // is frame-sized and receives - like rgb - the rows [own0, own1) of the frame only.  The whole-frame decode: 0, H, H, 0, 0, H.
+    int wy0, Hf, in_H, in_y0, own0, own1;
 };
 
 extern __shared__ float dsmem[];
@@ -300,7 +306,7 @@ struct Stager {
 
     __device__ __forceinline__ void init(const ConvArgs& a, int tid, int b, int x0, int y0) {
         const size_t img = (size_t)b * a.H * a.W;
-        inb = a.in + img * a.in_stride;   // (a frame's input is < 2^30 floats: checked on the host)
+        inb = a.in + ((size_t)b * a.in_H + a.in_y0) * a.W * a.in_stride;   // (a frame's input is < 2^30 floats: checked on the host)
         in2b = a.in2 ? a.in2 + img * a.in_stride : inb;
         if (FUSE) {
             fTb = a.fT + img * DEC_NF; fSb = a.fS ? a.fS + img * DEC_NF : nullptr; fXb = a.fX ? a.fX + img * DEC_NF : nullptr;
@@ -468,8 +474,8 @@ __global__ void __launch_bounds__(256, 5) k_conv16(ConvArgs a) {
     if (SEP) {   // the segment's channel sums: part[b][y * tilesX + bx][64]; a sum over the 16 lanes of a row group, both pixel halves
 #pragma unroll
         for (int q = 0; q < NR; ++q) {
-            const int y = y0 + wrow + q;
-            if (y >= a.H) continue;   // (wave-uniform)
+            const int y = y0 + wrow + q, yf = a.wy0 + y;
+            if (y >= a.H || yf < a.own0 || yf >= a.own1) continue;   // (wave-uniform)
             F4 sum;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -478,7 +484,7 @@ __global__ void __launch_bounds__(256, 5) k_conv16(ConvArgs a) {
                 for (int p = 0; p < NPH; ++p) v += (x0 + 16 * (ph + p) + pl < a.W) ? acc[p][q][k] : 0.f;
                 sum[k] = row16_sum(v);
             }
-            if (pl == 0) *(F4*)(a.se_part + (((size_t)b * a.H + y) * a.tilesX + bx) * DEC_NF + co) = sum;
+            if (pl == 0) *(F4*)(a.se_part + (((size_t)b * a.Hf + yf) * a.tilesX + bx) * DEC_NF + co) = sum;
         }
     }
     if (co >= a.cout) return;
@@ -494,14 +500,15 @@ __global__ void __launch_bounds__(256, 5) k_conv16(ConvArgs a) {
                                      : (size_t)b * a.H * a.W + (size_t)y * a.W + x;
             F4 v = acc[p][q];
             if (a.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-            if (a.rgb) {  // folded up stage: channel c = 3 s + o -> rgb[b][o][2y + (s >> 1)][2x + (s & 1)]
-                const int Ho = 2 * a.H, Wo = 2 * a.W;
+            if (a.rgb) {  // folded up stage: channel c = 3 s + o -> rgb[b][o][2y + (s >> 1)][2x + (s & 1)] (y: the frame's row)
+                const int Ho = 2 * a.Hf, Wo = 2 * a.W, yf = a.wy0 + y;
+                if (yf < a.own0 || yf >= a.own1) continue;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int c = co + k;
                     if (c < 12) {
                         const int sp = c / 3, o = c - 3 * sp;
-                        a.rgb[(((size_t)b * 3 + o) * Ho + 2 * y + (sp >> 1)) * Wo + 2 * x + (sp & 1)] = v[k];
+                        a.rgb[(((size_t)b * 3 + o) * Ho + 2 * yf + (sp >> 1)) * Wo + 2 * x + (sp & 1)] = v[k];
                     }
                 }
             } else {
@@ -618,11 +625,11 @@ __global__ void __launch_bounds__(256) k_conv3x3x(ConvArgs a) {
     const int x = x0 + j;
 #pragma unroll
     for (int q = 0; q < R; ++q) {
-        const int y = y0 + wrow0 + q;
+        const int y = y0 + wrow0 + q, yf = a.wy0 + y;
         if (y >= a.H) continue;   // (wave-uniform)
-        const bool valid = x < a.W;
-        if (SEP) {   // the segment's channel sums: part[b][y * tilesX + bx][64]
-            float* dst = a.se_part + (((size_t)b * a.H + y) * a.tilesX + bx) * DEC_NF + 32 * t + 4 * h;
+        const bool valid = x < a.W, owned = yf >= a.own0 && yf < a.own1;
+        if (SEP && owned) {   // the segment's channel sums: part[b][frame row * tilesX + bx][64]
+            float* dst = a.se_part + (((size_t)b * a.Hf + yf) * a.tilesX + bx) * DEC_NF + 32 * t + 4 * h;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 F4 sum;
@@ -641,13 +648,14 @@ __global__ void __launch_bounds__(256) k_conv3x3x(ConvArgs a) {
             F4 v = {acc[q][4 * g], acc[q][4 * g + 1], acc[q][4 * g + 2], acc[q][4 * g + 3]};
             if (a.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
             if (a.rgb) {
-                const int Ho = 2 * a.H, Wo = 2 * a.W;
+                const int Ho = 2 * a.Hf, Wo = 2 * a.W;
+                if (!owned) continue;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int c = co + k;
                     if (c < 12) {
                         const int s = c / 3, o = c - 3 * s;
-                        a.rgb[(((size_t)b * 3 + o) * Ho + 2 * y + (s >> 1)) * Wo + 2 * x + (s & 1)] = v[k];
+                        a.rgb[(((size_t)b * 3 + o) * Ho + 2 * yf + (s >> 1)) * Wo + 2 * x + (s & 1)] = v[k];
                     }
                 }
             } else {
@@ -754,51 +762,112 @@ static hipError_t launch_convx(const ConvArgs& a, int nt, hipStream_t st) {
     return hipGetLastError();
 }
 
-extern "C" int gdb_decode(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
-                          const float* d_packed, int32_t num_layers, int32_t precision, void* d_ws, size_t ws_bytes, float* d_rgb_c,
-                          void* stream_) {
+// ---- row windows ----------------------------------------------------------------------------------------------------------
+// A decode of the bundle-map rows [r0, r1) runs every convolution on the window [w0, w1) = [r0 - h, r1 + h) ∩ [0, H), its start rounded
+// down to DEC_WIN_ALIGN.  Every 3x3 convolution reads one row beyond the rows it writes, and a window edge that is not a frame edge reads
+// as zeros: each convolution leaves one more row at such an edge wrong.  in_conv, the 3 convolutions of each block and the up stage
+// (bundle_size 4: the sub-pixel stage at H, then the folded stage at 2H - half a bundle row, rounded up) are h = 1 + 3 L + log2(b)
+// convolutions, so the rows [r0, r1) - and each block's squeeze-excitation sums of them - are exact.  The window start is a multiple of
+// every workgroup tile height (2 rows fp32, 4 DECX_ROWS split-f16): the window's tiles are the frame's, and a pixel's arithmetic is the
+// whole-frame decode's, bit for bit.
+#define DEC_WIN_ALIGN 4
+static_assert(DEC_WIN_ALIGN % 2 == 0 && DEC_WIN_ALIGN % (4 * DECX_ROWS) == 0, "the window start must be a multiple of every tile height");
+static int dec_halo(int bundle_size, int nlayers) { return 1 + 3 * nlayers + (bundle_size == 4 ? 2 : 1); }
+static void dec_window(int bundle_size, int nlayers, int H, int r0, int r1, int* w0, int* w1) {
+    const int h = dec_halo(bundle_size, nlayers);
+    *w0 = (r0 - h > 0 ? r0 - h : 0) / DEC_WIN_ALIGN * DEC_WIN_ALIGN;
+    *w1 = r1 + h < H ? r1 + h : H;
+}
+static int dec_check_rows(const GdbConfig* cfg, const GdbFrame* shape, int32_t row_begin, int32_t row_end, int32_t num_layers) {
+    int rc = dec_check(cfg, num_layers); if (rc) return rc;
+    if (!shape) return gdb_fail(GDB_E_BADARG, "NULL pointer");
+    if (shape->B < 1 || shape->H < 1 || shape->W < 1) return gdb_fail(GDB_E_SHAPE, "non-positive bundle map");
+    if (row_begin >= row_end) return gdb_fail(GDB_E_BADARG, "empty row range [%d, %d)", row_begin, row_end);
+    if (row_begin < 0 || row_end > shape->H) return gdb_fail(GDB_E_SHAPE, "rows [%d, %d) outside the bundle map's %d", row_begin, row_end, shape->H);
+    return GDB_OK;
+}
+
+extern "C" int gdb_decoder_rows_workspace_bytes(const GdbConfig* cfg, const GdbFrame* shape, int32_t row_begin, int32_t row_end,
+                                                int32_t num_layers, size_t* out_bytes) {
+    int rc = dec_check_rows(cfg, shape, row_begin, row_end, num_layers); if (rc) return rc;
+    if (!out_bytes) return gdb_fail(GDB_E_BADARG, "NULL pointer");
+    int w0, w1;
+    dec_window(cfg->bundle_size, num_layers, shape->H, row_begin, row_end, &w0, &w1);
+    *out_bytes = dec_ws(shape->B, w1 - w0, shape->W, cfg->bundle_size, shape->H).total;
+    return GDB_OK;
+}
+
+extern "C" int gdb_decoder_rows_layout(const GdbConfig* cfg, const GdbFrame* shape, int32_t row_begin, int32_t row_end, int32_t num_layers,
+                                       size_t* part_offset, size_t* part_row_bytes, int32_t* window_begin, int32_t* window_end) {
+    int rc = dec_check_rows(cfg, shape, row_begin, row_end, num_layers); if (rc) return rc;
+    int w0, w1;
+    dec_window(cfg->bundle_size, num_layers, shape->H, row_begin, row_end, &w0, &w1);
+    const DecWs ws = dec_ws(shape->B, w1 - w0, shape->W, cfg->bundle_size, shape->H);
+    if (part_offset) *part_offset = ws.part;
+    if (part_row_bytes) *part_row_bytes = sizeof(float) * (size_t)((shape->W + 31) / 32) * DEC_NF;
+    if (window_begin) *window_begin = w0;
+    if (window_end) *window_end = w1;
+    return GDB_OK;
+}
+
+// Arguments common to gdb_decode and gdb_decode_rows, checked on the host before anything touches the device.
+static int dec_check_call(const GdbConfig* cfg, const GdbFrame* shape, int32_t ld_bundle_feat, int32_t num_layers, int32_t precision) {
     int rc = dec_check(cfg, num_layers); if (rc) return rc;
     if (precision != GDB_PREC_F32 && precision != GDB_PREC_F32X)
         return gdb_fail(GDB_E_BADARG, "decoder precision %d unsupported (1 = fp32 MFMA, 2 = split-f16 operand pairs)", precision);
-    const bool split = precision == GDB_PREC_F32X;
-    if (!shape || !d_bundle_feat || !d_packed || !d_ws || !d_rgb_c) return gdb_fail(GDB_E_BADARG, "NULL pointer");
+    if (!shape) return gdb_fail(GDB_E_BADARG, "NULL pointer");
     const int B = shape->B, H = shape->H, W = shape->W;
     if (B < 1 || H < 1 || W < 1) return gdb_fail(GDB_E_SHAPE, "non-positive bundle map");
     if (B > 256) return gdb_fail(GDB_E_SHAPE, "decoder batch %d > 256", B);
-    const int Q = 3 * cfg->bundle_size * cfg->bundle_size + GDB_CFR + GDB_CV, n_rgb = 3 * cfg->bundle_size * cfg->bundle_size;
+    const int Q = 3 * cfg->bundle_size * cfg->bundle_size + GDB_CFR + GDB_CV;
     if (ld_bundle_feat < Q) return gdb_fail(GDB_E_SHAPE, "bundle_feat row stride %d < %d channels", ld_bundle_feat, Q);
-    const bool up4 = cfg->bundle_size == 4;
-    const DecWs ws = dec_ws(B, H, W, cfg->bundle_size);
-    if (ws_bytes < ws.total) return gdb_fail(GDB_E_WORKSPACE, "decoder workspace %zu B < required %zu B", ws_bytes, ws.total);
-    if ((size_t)H * W * (up4 ? 4 : 1) * (size_t)(ld_bundle_feat > DEC_NF ? ld_bundle_feat : DEC_NF) >= ((size_t)1 << 30))
+    if ((size_t)H * W * (cfg->bundle_size == 4 ? 4 : 1) * (size_t)(ld_bundle_feat > DEC_NF ? ld_bundle_feat : DEC_NF) >= ((size_t)1 << 30))
         return gdb_fail(GDB_E_SHAPE, "bundle map too large for the decoder's 32-bit staging byte offsets");
+    return GDB_OK;
+}
+
+static std::atomic<unsigned long long> dec_attr_done{0};
+// per device, once: the split kernel's workgroup may take more than the default 64 KiB of dynamic LDS
+static int dec_split_attrs() {
+    const size_t lds = sizeof(unsigned) * ((size_t)(4 * DECX_ROWS + 2) * DEC_PX * DECX_PXD + 9 * 2 * 64 * 4);
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "hipGetDevice: %s", hipGetErrorString(e));
+    if (lds > 64 * 1024 && !(dec_attr_done.load() >> dev & 1)) {
+        const void* fns[] = {(const void*)k_conv3x3x<true, true, false>, (const void*)k_conv3x3x<true, false, true>,
+                             (const void*)k_conv3x3x<true, false, false>, (const void*)k_conv3x3x<false, false, false>};
+        for (const void* fn : fns) {
+            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+        }
+        dec_attr_done.fetch_or(1ull << dev);
+    }
+    return GDB_OK;
+}
+
+// Phases ph0 .. ph1 of the decode of rows [r0, r1) on the window [w0, w1) (the whole frame: 0, H, 0, H, phases 0 .. L).  Phase p:
+// p > 0 first runs block p-1's squeeze-excitation gate on the frame-sized `part`; p < L then runs block p's three convolutions (in_conv
+// first when p = 0); p = L runs the up stage(s) into d_rgb_c.  Phases 0 .. L in a row are gdb_decode's launch sequence.
+static int dec_phases(const GdbConfig* cfg, int B, int H, int W, const float* d_bundle_feat, int ld_bundle_feat, const float* d_packed,
+                      int num_layers, bool split, int r0, int r1, int w0, int w1, int ph0, int ph1, void* d_ws, float* d_rgb_c, hipStream_t st) {
+    const int Q = 3 * cfg->bundle_size * cfg->bundle_size + GDB_CFR + GDB_CV, n_rgb = 3 * cfg->bundle_size * cfg->bundle_size;
+    const bool up4 = cfg->bundle_size == 4;
+    const int Hw = w1 - w0;
+    const DecWs ws = dec_ws(B, Hw, W, cfg->bundle_size, H);
     const DecLayout L = dec_layout(num_layers, cfg->bundle_size);
-    hipStream_t st = (hipStream_t)stream_;
     float* Pbuf[3] = {(float*)((char*)d_ws + ws.P[0]), (float*)((char*)d_ws + ws.P[1]), (float*)((char*)d_ws + ws.P[2])};
     auto Px = [&](int b) -> float* { return b == 0 ? Pbuf[0] : Pbuf[1 + ((b - 1) & 1)]; };   // the input x of dense block b
     float* Y = (float*)((char*)d_ws + ws.Y); float* T = (float*)((char*)d_ws + ws.T);
     float* part = (float*)((char*)d_ws + ws.part); float* part2 = (float*)((char*)d_ws + ws.part2);
     float* gate = (float*)((char*)d_ws + ws.gate); unsigned* count = (unsigned*)((char*)d_ws + ws.count);
-    static std::atomic<unsigned long long> attr_done{0};
-    if (split) {   // per device, once: the split kernel's workgroup may take more than the default 64 KiB of dynamic LDS
-        const size_t lds = sizeof(unsigned) * ((size_t)(4 * DECX_ROWS + 2) * DEC_PX * DECX_PXD + 9 * 2 * 64 * 4);
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "hipGetDevice: %s", hipGetErrorString(e));
-        if (lds > 64 * 1024 && !(attr_done.load() >> dev & 1)) {
-            const void* fns[] = {(const void*)k_conv3x3x<true, true, false>, (const void*)k_conv3x3x<true, false, true>,
-                                 (const void*)k_conv3x3x<true, false, false>, (const void*)k_conv3x3x<false, false, false>};
-            for (const void* fn : fns) {
-                e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-            }
-            attr_done.fetch_or(1ull << dev);
-        }
-    }
-    int cH = H, cW = W;   // the map the next convolution runs on ((2H, 2W) for the last stage of upscale_factor 4)
+    // the map the next convolution runs on: window rows, its frame row origin, the frame's rows, the rows owned (all doubled for the
+    // last stage of upscale_factor 4, which runs on (2H, 2W))
+    int cH = Hw, cW = W, cy0 = w0, cHf = H, co0 = r0, co1 = r1;
     auto conv = [&](ConvArgs a, int nt) -> hipError_t {
         const int H = cH, W = cW;
         a.B = B; a.H = H; a.W = W; a.tilesX = (W + 31) / 32;
+        a.wy0 = cy0; a.Hf = cHf; a.own0 = co0; a.own1 = co1;
+        if (!a.in_H) a.in_H = H;   // (in_conv sets the frame's rows and the window origin: it reads the bundle rows in place)
         a.nchunk = (a.cin + 31) / 32;
         if (!a.in2) a.split = a.nchunk;
         a.vec = (a.in_stride % 4 == 0) && (a.in_off % 4 == 0) && (a.cin % 4 == 0) && ((uintptr_t)a.in % 16 == 0);
@@ -812,62 +881,101 @@ extern "C" int gdb_decode(const GdbConfig* cfg, const GdbFrame* shape, const flo
     };
     hipError_t e;
 #define CK(x) do { e = (x); if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "decoder launch: %s", hipGetErrorString(e)); } while (0)
-    {   // shallow = in_conv(bundle channels n_rgb..Q-1)   decoder_rdn.py:76: block 0's x, and the global residual at the end
-        ConvArgs a{};
-        a.in = d_bundle_feat; a.in_stride = ld_bundle_feat; a.in_off = n_rgb; a.cin = Q - n_rgb;
-        a.w = d_packed + (split ? L.in_wx : L.in_w); a.bias = d_packed + L.in_b;
-        a.out = Px(0); a.out_stride = DEC_NF; a.out_off = 0; a.cout = DEC_NF; a.relu = 0; a.zero = count;
-        CK(conv(a, 2));
-    }
-    for (int b = 0; b < num_layers; ++b) {   // ResidualDenseBlock.forward   decoder_rdn.py:35-41
-        ConvArgs a{};
-        a.in_stride = DEC_NF; a.in_off = 0; a.out = Y; a.out_stride = DEC_NF; a.relu = 1;
-        // conv1; from the second block on it first forms its own input x_b = x_{b-1} + x3_{b-1} * gate_{b-1} (:40) and leaves it in P[b]
-        a.in = b ? Px(b - 1) : Px(0);
-        if (b) { a.fT = T; a.fgate = gate; a.fX = Px(b); }
-        a.cin = DEC_NF; a.w = d_packed + (split ? L.blkx[b][0] : L.blk[b][0]); a.out_off = 0; a.cout = DEC_G;
-        CK(conv(a, 1));
-        a.fT = nullptr; a.fgate = nullptr; a.fX = nullptr;
-        a.in = Px(b); a.in2 = Y; a.split = 2;
-        a.cin = DEC_NF + DEC_G; a.w = d_packed + (split ? L.blkx[b][1] : L.blk[b][1]); a.out_off = DEC_G;
-        CK(conv(a, 1));
-        a.cin = DEC_NF + 2 * DEC_G; a.w = d_packed + (split ? L.blkx[b][2] : L.blk[b][2]); a.out = T; a.out_off = 0; a.cout = DEC_NF; a.relu = 0;
-        a.se_part = part;
-        CK(conv(a, 2));
-        hipLaunchKernelGGL(k_se_gate, dim3((unsigned)(B * ws.ngrp)), dim3(256), 0, st, part, ws.nseg, ws.ngrp, 1.f / (float)((size_t)H * W),
-                           d_packed + L.blk[b][3], d_packed + L.blk[b][4], part2, count, gate);
-        CK(hipGetLastError());
-    }
-    if (!up4) {   // out_conv(PixelShuffle(up(x + shallow))) as one folded 64 -> 12 convolution on x = x_{L-1} + x3 * gate + shallow   :40,78-80
-        ConvArgs a{};
-        a.in = Px(num_layers - 1); a.in_stride = DEC_NF; a.in_off = 0; a.cin = DEC_NF;
-        a.fT = T; a.fgate = gate; a.fS = Px(0);
-        a.w = d_packed + (split ? L.up_wx : L.up_w); a.bias = d_packed + L.up_b;
-        a.cout = 12; a.relu = 0; a.rgb = d_rgb_c;
-        CK(conv(a, 1));
-    } else {
-        // upscale_factor 4 (bundle_size 4; decoder_rdn.py:59-62): x = x_{L-1} + x3 * gate + shallow as its own pass, the first up stage as
-        // four 64 -> 64 convolutions (one per sub-pixel of its PixelShuffle) into the (2H, 2W, 64) map U, then the second stage folded with
-        // out_conv as ONE 64 -> 12 convolution on U, written pixel-shuffled to the (4H, 4W) image - no non-linearity anywhere in between.
-        float* X = (float*)((char*)d_ws + ws.X); float* U = (float*)((char*)d_ws + ws.U);
-        const size_t npix = (size_t)H * W;
-        hipLaunchKernelGGL(k_apply_gate, dim3((unsigned)(((size_t)B * npix * 16 + 255) / 256)), dim3(256), 0, st, Px(num_layers - 1), T, gate, Px(0), X, npix, B);
-        CK(hipGetLastError());
-        for (int sp = 0; sp < 4; ++sp) {
+    for (int ph = ph0; ph <= ph1; ++ph) {
+        if (ph > 0) {   // squeeze-excitation of block ph-1 on the frame's channel sums   decoder_rdn.py:17-21
+            const int b = ph - 1;
+            hipLaunchKernelGGL(k_se_gate, dim3((unsigned)(B * ws.ngrp)), dim3(256), 0, st, part, ws.nseg, ws.ngrp, 1.f / (float)((size_t)H * W),
+                               d_packed + L.blk[b][3], d_packed + L.blk[b][4], part2, count, gate);
+            CK(hipGetLastError());
+        }
+        if (ph == 0) {   // shallow = in_conv(bundle channels n_rgb..Q-1)   decoder_rdn.py:76: block 0's x, and the global residual at the end
             ConvArgs a{};
-            a.in = X; a.in_stride = DEC_NF; a.in_off = 0; a.cin = DEC_NF;
-            a.w = d_packed + (split ? L.u1_wx[sp] : L.u1_w[sp]); a.bias = d_packed + L.u1_b[sp];
-            a.out = U; a.out_stride = DEC_NF; a.out_off = 0; a.cout = DEC_NF; a.relu = 0;
-            a.up2 = 1; a.up_dy = sp >> 1; a.up_dx = sp & 1;
+            a.in = d_bundle_feat; a.in_stride = ld_bundle_feat; a.in_off = n_rgb; a.cin = Q - n_rgb; a.in_H = H; a.in_y0 = w0;
+            a.w = d_packed + (split ? L.in_wx : L.in_w); a.bias = d_packed + L.in_b;
+            a.out = Px(0); a.out_stride = DEC_NF; a.out_off = 0; a.cout = DEC_NF; a.relu = 0; a.zero = count;
             CK(conv(a, 2));
         }
-        cH = 2 * H; cW = 2 * W;
-        ConvArgs a{};
-        a.in = U; a.in_stride = DEC_NF; a.in_off = 0; a.cin = DEC_NF;
-        a.w = d_packed + (split ? L.up_wx : L.up_w); a.bias = d_packed + L.up_b;
-        a.cout = 12; a.relu = 0; a.rgb = d_rgb_c;
-        CK(conv(a, 1));
+        if (ph < num_layers) {   // ResidualDenseBlock.forward   decoder_rdn.py:35-41 (its gate: the next phase)
+            const int b = ph;
+            ConvArgs a{};
+            a.in_stride = DEC_NF; a.in_off = 0; a.out = Y; a.out_stride = DEC_NF; a.relu = 1;
+            // conv1; from the second block on it first forms its own input x_b = x_{b-1} + x3_{b-1} * gate_{b-1} (:40) and leaves it in P[b]
+            a.in = b ? Px(b - 1) : Px(0);
+            if (b) { a.fT = T; a.fgate = gate; a.fX = Px(b); }
+            a.cin = DEC_NF; a.w = d_packed + (split ? L.blkx[b][0] : L.blk[b][0]); a.out_off = 0; a.cout = DEC_G;
+            CK(conv(a, 1));
+            a.fT = nullptr; a.fgate = nullptr; a.fX = nullptr;
+            a.in = Px(b); a.in2 = Y; a.split = 2;
+            a.cin = DEC_NF + DEC_G; a.w = d_packed + (split ? L.blkx[b][1] : L.blk[b][1]); a.out_off = DEC_G;
+            CK(conv(a, 1));
+            a.cin = DEC_NF + 2 * DEC_G; a.w = d_packed + (split ? L.blkx[b][2] : L.blk[b][2]); a.out = T; a.out_off = 0; a.cout = DEC_NF; a.relu = 0;
+            a.se_part = part;
+            CK(conv(a, 2));
+            continue;
+        }
+        if (!up4) {   // out_conv(PixelShuffle(up(x + shallow))) as one folded 64 -> 12 convolution on x = x_{L-1} + x3 * gate + shallow   :40,78-80
+            ConvArgs a{};
+            a.in = Px(num_layers - 1); a.in_stride = DEC_NF; a.in_off = 0; a.cin = DEC_NF;
+            a.fT = T; a.fgate = gate; a.fS = Px(0);
+            a.w = d_packed + (split ? L.up_wx : L.up_w); a.bias = d_packed + L.up_b;
+            a.cout = 12; a.relu = 0; a.rgb = d_rgb_c;
+            CK(conv(a, 1));
+        } else {
+            // upscale_factor 4 (bundle_size 4; decoder_rdn.py:59-62): x = x_{L-1} + x3 * gate + shallow as its own pass, the first up stage as
+            // four 64 -> 64 convolutions (one per sub-pixel of its PixelShuffle) into the (2H, 2W, 64) map U, then the second stage folded with
+            // out_conv as ONE 64 -> 12 convolution on U, written pixel-shuffled to the (4H, 4W) image - no non-linearity anywhere in between.
+            float* X = (float*)((char*)d_ws + ws.X); float* U = (float*)((char*)d_ws + ws.U);
+            const size_t npix = (size_t)Hw * W;
+            hipLaunchKernelGGL(k_apply_gate, dim3((unsigned)(((size_t)B * npix * 16 + 255) / 256)), dim3(256), 0, st, Px(num_layers - 1), T, gate, Px(0), X, npix, B);
+            CK(hipGetLastError());
+            for (int sp = 0; sp < 4; ++sp) {
+                ConvArgs a{};
+                a.in = X; a.in_stride = DEC_NF; a.in_off = 0; a.cin = DEC_NF;
+                a.w = d_packed + (split ? L.u1_wx[sp] : L.u1_w[sp]); a.bias = d_packed + L.u1_b[sp];
+                a.out = U; a.out_stride = DEC_NF; a.out_off = 0; a.cout = DEC_NF; a.relu = 0;
+                a.up2 = 1; a.up_dy = sp >> 1; a.up_dx = sp & 1;
+                CK(conv(a, 2));
+            }
+            cH = 2 * Hw; cW = 2 * W; cy0 = 2 * w0; cHf = 2 * H; co0 = 2 * r0; co1 = 2 * r1;
+            ConvArgs a{};
+            a.in = U; a.in_stride = DEC_NF; a.in_off = 0; a.cin = DEC_NF;
+            a.w = d_packed + (split ? L.up_wx : L.up_w); a.bias = d_packed + L.up_b;
+            a.cout = 12; a.relu = 0; a.rgb = d_rgb_c;
+            CK(conv(a, 1));
+        }
     }
 #undef CK
     return GDB_OK;
+}
+
+extern "C" int gdb_decode(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
+                          const float* d_packed, int32_t num_layers, int32_t precision, void* d_ws, size_t ws_bytes, float* d_rgb_c,
+                          void* stream_) {
+    int rc = dec_check_call(cfg, shape, ld_bundle_feat, num_layers, precision); if (rc) return rc;
+    if (!d_bundle_feat || !d_packed || !d_ws || !d_rgb_c) return gdb_fail(GDB_E_BADARG, "NULL pointer");
+    const int B = shape->B, H = shape->H, W = shape->W;
+    const DecWs ws = dec_ws(B, H, W, cfg->bundle_size);
+    if (ws_bytes < ws.total) return gdb_fail(GDB_E_WORKSPACE, "decoder workspace %zu B < required %zu B", ws_bytes, ws.total);
+    const bool split = precision == GDB_PREC_F32X;
+    if (split && (rc = dec_split_attrs())) return rc;
+    return dec_phases(cfg, B, H, W, d_bundle_feat, ld_bundle_feat, d_packed, num_layers, split, 0, H, 0, H, 0, num_layers, d_ws, d_rgb_c,
+                      (hipStream_t)stream_);
+}
+
+extern "C" int gdb_decode_rows(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
+                               const float* d_packed, int32_t num_layers, int32_t precision, int32_t row_begin, int32_t row_end,
+                               int32_t phase, void* d_ws, size_t ws_bytes, float* d_rgb_c, void* stream_) {
+    int rc = dec_check_call(cfg, shape, ld_bundle_feat, num_layers, precision); if (rc) return rc;
+    if (phase < 0 || phase > num_layers) return gdb_fail(GDB_E_BADARG, "decoder phase %d outside 0..%d", phase, num_layers);
+    rc = dec_check_rows(cfg, shape, row_begin, row_end, num_layers); if (rc) return rc;
+    if (!d_bundle_feat || !d_packed || !d_ws || (phase == num_layers && !d_rgb_c)) return gdb_fail(GDB_E_BADARG, "NULL pointer");
+    const int B = shape->B, H = shape->H, W = shape->W;
+    int w0, w1;
+    dec_window(cfg->bundle_size, num_layers, H, row_begin, row_end, &w0, &w1);
+    const DecWs ws = dec_ws(B, w1 - w0, W, cfg->bundle_size, H);
+    if (ws_bytes < ws.total) return gdb_fail(GDB_E_WORKSPACE, "decoder workspace %zu B < required %zu B", ws_bytes, ws.total);
+    const bool split = precision == GDB_PREC_F32X;
+    if (split && (rc = dec_split_attrs())) return rc;
+    return dec_phases(cfg, B, H, W, d_bundle_feat, ld_bundle_feat, d_packed, num_layers, split, row_begin, row_end, w0, w1, phase, phase,
+                      d_ws, d_rgb_c, (hipStream_t)stream_);
 }

@@ -431,6 +431,43 @@ class HotPathEngine:
                                        self.dec_layers, int(precision), self._dec_ws.data_ptr(), self._dec_ws.numel(), rgb_c.data_ptr(), self._stream()))
         return rgb_c
 
+    def decoder_rows(self, row_begin: int, row_end: int) -> "DecodeRows":
+        """A row-window decode of the bundle rows [row_begin, row_end) of the frame last prepared (`nerf.shard: tiles`): see DecodeRows."""
+        if getattr(self, "dec_weights", None) is None:
+            raise ValueError("load_decoder_weights() first")
+        return DecodeRows(self, row_begin, row_end)
+
+    @_on_device
+    def merge_packed_rows(self, packed: torch.Tensor, rgb_c: Optional[torch.Tensor], reweighting: bool, row_begin: int, row_end: int,
+                          tile: torch.Tensor) -> torch.Tensor:
+        """The image of `merge_packed` for the bundle rows [row_begin, row_end) only, into rows 0 .. (row_end - row_begin) b of
+        `tile` (B, 3, tile_rows b, Wo) (gdb_merge_packed_rows).  rgb_c: the frame-sized decoder image, read on the strip's rows."""
+        f = self._need_frame()
+        b = self.cfg.bundle_size
+        _chk(packed, "packed", (self.n_bundles, self.Q + 2))
+        if rgb_c is not None:
+            _chk(rgb_c, "rgb_c", (f.B, 3, f.H * b, f.W * b))
+        if tile.dim() != 4 or tuple(tile.shape[:2]) != (f.B, 3) or tile.shape[2] % b or tile.shape[3] != f.W * b:
+            raise ValueError(f"tile has shape {tuple(tile.shape)}, expected ({f.B}, 3, rows * {b}, {f.W * b})")
+        _chk(tile, "tile")
+        _lib.check(self.lib.gdb_merge_packed_rows(C.byref(self.cfg), C.byref(f), packed.data_ptr(), _ptr(rgb_c), int(bool(reweighting)),
+                                                  int(row_begin), int(row_end), int(tile.shape[2] // b), tile.data_ptr(), self._stream()))
+        return tile
+
+    @_on_device
+    def upsample_maps(self, maps: torch.Tensor):
+        """The bilinear x b upsampling of `merge` alone (gdb_upsample_maps): maps (n_bundles, C >= 2) with depth in column 0 and
+        opacity in column 1 -> (depth, opacity), each (B, Ho, Wo)."""
+        f = self._need_frame()
+        b = self.cfg.bundle_size
+        if maps.dim() != 2 or maps.shape[0] != self.n_bundles or maps.shape[1] < 2:
+            raise ValueError(f"maps has shape {tuple(maps.shape)}, expected ({self.n_bundles}, >= 2)")
+        _chk(maps, "maps")
+        dep, opa = self._buf("merge.bundle_depth", (f.B, f.H * b, f.W * b)), self._buf("merge.bundle_opacity", (f.B, f.H * b, f.W * b))
+        _lib.check(self.lib.gdb_upsample_maps(C.byref(self.cfg), C.byref(f), maps.data_ptr(), int(maps.shape[1]), dep.data_ptr(),
+                                              opa.data_ptr(), self._stream()))
+        return dep, opa
+
     def set_schedule(self, mode: int) -> None:
         """Work decomposition of THIS engine's fused calls (a per-call argument of the C ABI, no process-wide state):
         0 auto, 1 one wave per sample slot, 2 one wave per 32-bundle segment, 3 dense (one wave per window of whole bundles holding
@@ -694,3 +731,47 @@ class HotPathEngine:
                                                       int(row_begin), int(row_end), int(precision), self._sched(row_begin, row_end),
                                                       out.data_ptr(), self._stream()))
         return out
+
+
+class DecodeRows:
+    """The decoder on the bundle rows [r0, r1) of the frame `eng` last prepared (gdb_decode_rows), for a frame split over ranks.
+
+        dec = eng.decoder_rows(r0, r1)         # owns the window's workspace; dec.window = rows to render, dec.part = (B, H, P) sums
+        for p in range(dec.phases):            # num_layers + 1 phases
+            if p: <all-gather the owned rows of dec.part>    (parallel.PartialsGather)
+            rgb_c = dec.run_phase(packed, p)   # None before the last phase, then the frame-sized (B, 3, Ho, Wo) image
+
+    Only rows [r0 b, r1 b) of rgb_c are written; they are bit-identical to `eng.decode` on the whole frame.  `packed` must hold the
+    window's rows.  The decode's precision is the engine's, as in `decode`, unless given."""
+
+    def __init__(self, eng: HotPathEngine, r0: int, r1: int):
+        f = eng._need_frame()
+        self.eng, self.r0, self.r1 = eng, int(r0), int(r1)
+        self.shape = (f.B, f.H, f.W)
+        need, off, pitch, w0, w1 = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int32(), C.c_int32()
+        _lib.check(eng.lib.gdb_decoder_rows_workspace_bytes(C.byref(eng.cfg), C.byref(f), self.r0, self.r1, eng.dec_layers, C.byref(need)))
+        _lib.check(eng.lib.gdb_decoder_rows_layout(C.byref(eng.cfg), C.byref(f), self.r0, self.r1, eng.dec_layers, C.byref(off), C.byref(pitch),
+                                                   C.byref(w0), C.byref(w1)))
+        self.window = (w0.value, w1.value)
+        self.phases = eng.dec_layers + 1
+        self.ws = torch.empty(need.value, dtype=torch.uint8, device=eng.device)
+        n = f.B * f.H * pitch.value
+        self.part = self.ws[off.value: off.value + n].view(torch.float32).view(f.B, f.H, pitch.value // 4)
+        b = eng.cfg.bundle_size
+        self.rgb_c = torch.empty((f.B, 3, f.H * b, f.W * b), dtype=torch.float32, device=eng.device)
+
+    def run_phase(self, packed: torch.Tensor, phase: int, precision: Optional[int] = None) -> Optional[torch.Tensor]:
+        eng = self.eng
+        if precision is None:
+            precision = _lib.PREC_F32 if eng.precision == _lib.PREC_F32 else _lib.PREC_F32X
+        f = eng._need_frame()
+        if (f.B, f.H, f.W) != self.shape:
+            raise ValueError(f"the engine's frame {(f.B, f.H, f.W)} is not the one this decode was planned for {self.shape}")
+        if packed.dim() != 2 or packed.shape[0] != eng.n_bundles or packed.shape[1] < eng.Q:
+            raise ValueError(f"bundle_feat has shape {tuple(packed.shape)}, expected ({eng.n_bundles}, >= {eng.Q})")
+        _chk(packed, "bundle_feat")
+        with torch.cuda.device(eng.device):
+            _lib.check(eng.lib.gdb_decode_rows(C.byref(eng.cfg), C.byref(f), packed.data_ptr(), int(packed.shape[1]), eng.dec_weights.data_ptr(),
+                                               eng.dec_layers, int(precision), self.r0, self.r1, int(phase), self.ws.data_ptr(), self.ws.numel(),
+                                               self.rgb_c.data_ptr(), eng._stream()))
+        return self.rgb_c if phase == self.phases - 1 else None

@@ -13,7 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ...engine import HotPathEngine
-from ...parallel import StripGather, gather_strips
+from ...parallel import PartialsGather, StripGather, TileGather, decode_window, decoder_halo, gather_strips, row_strip, se_partial_pitch
 from . import utils
 from .bundle_sampler import BundleSampler
 from .decoder_rdn import Decoder
@@ -62,9 +62,19 @@ class Network(nn.Module):
         # bundle-map rows of the frame and ONE all-gather of the packed rows (RCCL over xGMI) leaves the whole bundle map on every
         # rank; decoder and merge then run replicated (the decoder's squeeze-excitation takes a global mean over the image,
         # decoder_rdn.py:10,20, so it does not shard by rows).  "none" (default): every rank renders whole frames.
+        # "tiles": each rank renders its strip plus the decoder's halo (parallel.decode_window), decodes its strip by row windows
+        # with one all-gather of the squeeze-excitation sums per dense block (the mean's only non-local input), merges its strip,
+        # and ONE all-gather of the image tiles with the bundle-resolution depth and opacity (3 b^2 + 2 floats per bundle) leaves
+        # the frame on every rank.  Needs the HIP decoder and the fused hot path.  The FPN and the depth net stay replicated.
         self.shard = str(getattr(nrf, "shard", "none"))
-        if self.shard not in ("none", "rows"):
-            raise ValueError(f"nerf.shard must be 'none' or 'rows', got {self.shard!r}")
+        if self.shard not in ("none", "rows", "tiles"):
+            raise ValueError(f"nerf.shard must be 'none', 'rows' or 'tiles', got {self.shard!r}")
+        if self.shard == "tiles" and not self.hip_decoder:
+            raise ValueError("nerf.shard 'tiles' shards the HIP decoder by rows: it needs nerf.hip_decoder with bundle_size 2 or 4 and "
+                             f"dec_layers 1..16 (got hip_decoder {bool(getattr(nrf, 'hip_decoder', True))}, bundle_size {self.b_size}, "
+                             f"dec_layers {self.dec_layers})")
+        if self.shard == "tiles" and self.hot_path != "fused":
+            raise ValueError(f"nerf.shard 'tiles' needs nerf.hot_path 'fused' (got {self.hot_path!r}): the operator mirrors render whole frames")
         # The intermediates of a frame (packed render, decoder image) always live in per-engine buffers reused frame after frame.
         # The tensors in the returned dict are fresh by default, as the reference's are (a caller may keep them across frames);
         # `nerf.reuse_outputs: true` makes them per-engine buffers too, overwritten by the next forward: no allocation at all in
@@ -73,6 +83,7 @@ class Network(nn.Module):
         self._feat_dim = feat_dim
         self._engine = None
         self._gather = None
+        self._tiles_state = None
 
     # ---- hot path ------------------------------------------------------------------------
     def _get_engine(self, device) -> HotPathEngine:
@@ -107,7 +118,7 @@ class Network(nn.Module):
 
     def _dist(self):
         """torch.distributed when this forward is to be row-sharded, else None."""
-        if self.shard != "rows":
+        if self.shard not in ("rows", "tiles"):
             return None
         import torch.distributed as dist
         return dist if dist.is_available() and dist.is_initialized() else None
@@ -141,6 +152,44 @@ class Network(nn.Module):
         if stage and full.is_cuda:
             return gather_strips(full.cpu(), H, world, dist, B=B).to(full.device)
         return gather_strips(full, H, world, dist, B=B)
+
+    def _forward_tiles(self, eng, B: int, H: int, W: int, dist):
+        """`nerf.shard: tiles` on the prepared frame: this rank's window render, its strip's decode in num_layers + 1 phases with one
+        all-gather of the squeeze-excitation sums between each, its strip's merge, then ONE all-gather of the tiles.  Returns the
+        frame's (img, nerf_depth, opacity) on every rank, bit-identical to `shard: none`."""
+        world, rank = dist.get_world_size(), dist.get_rank()
+        b, L, Q = self.b_size, int(self.dec_layers), eng.Q
+        r0, r1 = row_strip(H, rank, world)
+        w0, w1 = decode_window(H, rank, world, decoder_halo(b, L))
+        stage = dist.get_backend() == "gloo"   # gloo exchanges host copies, as `rows` does
+        key = (B, H, W, world, rank, str(eng.device), id(eng))
+        st = self._tiles_state
+        if st is None or st["key"] != key:
+            dec = eng.decoder_rows(r0, r1) if r1 > r0 else None
+            if dec is not None and dec.window != (w0, w1):
+                raise RuntimeError(f"decoder window {dec.window} != parallel.decode_window {(w0, w1)}")
+            part = dec.part if dec is not None else torch.zeros((B, H, se_partial_pitch(W)), device=eng.device)
+            st = self._tiles_state = {"key": key, "dec": dec, "packed": torch.zeros((B * H * W, Q + 2), device=eng.device),
+                                      "partials": PartialsGather(part, world, rank, dist, stage_cpu=stage),
+                                      "tiles": TileGather(B, H, W, b, world, rank, eng.device, dist, stage_cpu=stage)}
+        dec, packed, pg, tg = st["dec"], st["packed"], st["partials"], st["tiles"]
+        if dec is not None:
+            if eng.fused_supported:
+                eng.render_packed(w0, w1, None, packed)   # the halo rows are re-rendered here: bundles are independent
+            else:
+                packed = eng.render_unfused_packed()      # (the operator mirrors take no row range: the whole frame)
+        rgb_c = None
+        for p in range(L + 1):
+            if p:
+                pg.gather()
+            if dec is not None:
+                rgb_c = dec.run_phase(packed, p)
+        if dec is not None:
+            eng.merge_packed_rows(packed, rgb_c, self.reweighting, r0, r1, tg.tile)
+            tg.maps[:, : r1 - r0].copy_(packed.view(B, H, W, Q + 2)[:, r0:r1, :, Q:Q + 2])
+        img, maps = tg.gather()
+        nerf_depth, opacity = eng.upsample_maps(maps)
+        return img, nerf_depth, opacity
 
     def render_bundles(self, rgbs_feat_rgb_dir, vox_feat, z_vals, indices, samples_per_bundle):
         """MLP + normalised alpha composite on materialised samples (reference network.py:54-91)."""
@@ -192,13 +241,18 @@ class Network(nn.Module):
             # launch to pay - builds only the strip's reach of the pyramids (gdb_prepare_rows; any bundle size)
             dist = self._dist()
             rows = None
-            if dist is not None:
-                from ...parallel import row_strip
+            if dist is not None and self.shard == "tiles":   # the strip plus the decoder's halo (an empty strip plans the frame)
+                rows = decode_window(H, dist.get_rank(), dist.get_world_size(), decoder_halo(b, int(self.dec_layers)))
+                rows = rows if rows[1] > rows[0] else None
+            elif dist is not None:
                 rows = row_strip(H, dist.get_rank(), dist.get_world_size())
             # N3: the kernel resamples the colour channels itself (no torch.cat / F.interpolate of the source images)
             eng.prepare({"src_images": c(src_images), "fpn_feat": c(img_feat), "feat_volume": c(feat_volume),
                          "depth_range": c(depth_range), "vol_range": c(vol_range), "src_exts": c(src_exts), "src_ints": c(src_ints),
                          "tar_ext": c(tar_exts), "tar_int": c(tar_ints), "near_far": c(near_far)}, rows=rows)
+            if dist is not None and self.shard == "tiles":
+                img, nerf_depth, opacity = self._forward_tiles(eng, B, H, W, dist)
+                return {"rgb": img, "nerf_depth": nerf_depth, "mvs_depth": mvs_depth, "opacity": opacity}, mvs_depths, blend_rgbs
             packed = self._render_packed(eng, B, H, W)
             if self.hip_decoder:
                 rgb_c = eng.decode(packed)   # reads channels 3 b^2 .. Q-1 of the packed rows in place

@@ -32,6 +32,7 @@
 extern "C" {
 #endif
 
+/* v7 grew additively after its release: entries marked "(ABI v7, added)" are new functions, no existing signature or layout changed. */
 #define GDB_ABI_VERSION 7
 
 typedef enum GdbStatus {
@@ -375,6 +376,15 @@ int gdb_merge(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle
  * place: the buffer a row-strip all-gather leaves on every rank (network.py:170-182 after the exchange of SURVEY.md 8(e)). */
 int gdb_merge_packed(const GdbConfig* cfg, const GdbFrame* shape, const float* d_packed, const float* d_rgb_c, int32_t reweighting,
                      float* d_img, float* d_out_depth, float* d_out_opacity, void* stream);
+/* (ABI v7, added) The image of gdb_merge_packed for the bundle rows [row_begin, row_end) only, written to d_tile (B,3,tile_rows*b,W*b)
+ * from its row 0 (tile rows beyond the strip are left as they are): one rank's share of a frame decoded by row windows
+ * (gdb_decode_rows; d_rgb_c is the frame-sized (B,3,H*b,W*b) buffer, only the strip's rows are read).  Bit-identical per pixel to
+ * gdb_merge_packed.  gdb_upsample_maps: the depth / opacity upsampling of gdb_merge alone, on d_maps = B*H*W rows of map_stride
+ * floats, depth in column 0 and opacity in column 1 (what a gather of the ranks' bundle-resolution maps leaves). */
+int gdb_merge_packed_rows(const GdbConfig* cfg, const GdbFrame* shape, const float* d_packed, const float* d_rgb_c, int32_t reweighting,
+                          int32_t row_begin, int32_t row_end, int32_t tile_rows, float* d_tile, void* stream);
+int gdb_upsample_maps(const GdbConfig* cfg, const GdbFrame* shape, const float* d_maps, int32_t map_stride, float* d_out_depth,
+                      float* d_out_opacity, void* stream);
 
 /* ---- the decoder itself (next row N1) --------------------------------------------------- */
 /* Decoder.forward, networks/gdb_nerf/decoder_rdn.py:44-81 (instantiated at network.py:51 as Decoder(C_f+3+C_v, 3, num_feats=64,
@@ -402,6 +412,26 @@ int gdb_decoder_workspace_bytes(const GdbConfig* cfg, const GdbFrame* shape, siz
 int gdb_decode(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
                const float* d_packed_decoder_weights, int32_t num_layers, int32_t precision, void* d_workspace,
                size_t workspace_bytes, float* d_rgb_c, void* stream);
+
+/* ---- the decoder by row windows (ABI v7, added) -------------------------------------------- */
+/* The decode of the bundle-map rows [row_begin, row_end) alone, for a frame whose rows are split over ranks.  The library holds no
+ * communicator, so the decode returns to the caller at every squeeze-excitation (its mean runs over the whole image): phase p of
+ * 0 .. num_layers first runs the gate of block p-1 (p > 0) on the workspace's frame-sized channel-sum buffer `part`, then block p's
+ * three convolutions (in_conv first when p = 0; their sums are written to `part` for the owned rows only, at their frame row), and
+ * phase num_layers the up stage(s), writing rows [row_begin*b, row_end*b) of the frame-sized d_rgb_c (B,3,H*b,W*b) only (d_rgb_c may
+ * be NULL before that phase).  Between phases the caller fills the other rows of `part` (an all-gather of every rank's owned rows).
+ * The convolutions run on a window [row_begin - h, row_end + h) ∩ [0, H), start rounded down to a multiple of 4, with
+ * h = 1 + 3 num_layers + log2(b) rows: d_bundle_feat (frame-sized, as for gdb_decode) must hold the window's rows.  The rows
+ * written are bit-identical to gdb_decode's on the whole frame, at both precisions.
+ * gdb_decoder_rows_layout: the byte offset of `part` in the workspace and its row pitch (part is (B, H, pitch) floats: item b, row y
+ * at offset + (b H + y) pitch_bytes), and the window [*window_begin, *window_end); any out pointer may be NULL. */
+int gdb_decoder_rows_workspace_bytes(const GdbConfig* cfg, const GdbFrame* shape, int32_t row_begin, int32_t row_end,
+                                     int32_t num_layers, size_t* out_bytes);
+int gdb_decoder_rows_layout(const GdbConfig* cfg, const GdbFrame* shape, int32_t row_begin, int32_t row_end, int32_t num_layers,
+                            size_t* part_offset, size_t* part_row_bytes, int32_t* window_begin, int32_t* window_end);
+int gdb_decode_rows(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
+                    const float* d_packed_decoder_weights, int32_t num_layers, int32_t precision, int32_t row_begin, int32_t row_end,
+                    int32_t phase, void* d_workspace, size_t workspace_bytes, float* d_rgb_c, void* stream);
 
 #ifdef __cplusplus
 }
