@@ -1,27 +1,31 @@
 #!/usr/bin/env python3
 """Benchmark of the GDB-NeRF hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2] [--precision f32|f16|f32x] [--path fused|unfused] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload c2] [--precision f32|f16|f32x] [--path fused|unfused] [--dump-outputs DIR] [--full]
 
 One *step* = one pass of the hot path (per-frame preparation: camera block + feature mip pyramid; then
 build_rays → sample → encode → MLP → composite) over one synthetic frame of the workload, inputs already
 resident in HBM.  Metric: rendered rays per second, whole job.
 
 Headline (N = 1): workload c2 = BASELINE.json configs[1] at `--precision f32` — the NeRF MLP on fp32 MFMA, the
-reference's own precision (nerf.py:84-115 never leaves fp32).  The f16-operand path is timed in the same run and
-reported as the `secondary` record.  The JSON line also carries `psnr_delta_db` (fused render vs the exact-fp32
-operator chain on the benched frame), `hbm_frac` / `mfma_frac` against vendor peaks, `peaks_measured` (stream
-triad and bare MFMA loops run on this node), `t_frame_ms` (whole Network.forward, the reference's run.py:56-73
-protocol), `roofline` and `cpu_baseline`.
+reference's own precision (nerf.py:84-115 never leaves fp32).
 
-N > 1 (launched by torch.distributed.run, one rank per GPU), both modes timed in one run:
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs if --dump-outputs is
+given, print the line.  `--full` adds everything else, after the timed steps: `hbm_frac` / `mfma_frac` against vendor peaks
+and the `roofline` (the dominant kernel timed in runs of its own); the other precisions (`secondary`: the f16-operand
+path), `psnr_delta_db` (fused render vs the oracle and vs the exact-fp32 operator chain), the S_max 8, two-stream,
+bundle-size 4, sources-ready and HIP-graph records, `peaks_measured` (stream triad and bare MFMA loops run on this node),
+`t_frame_ms` (whole Network.forward, the reference's run.py:56-73 protocol) and `cpu_baseline`; at N > 1 the mode that is not
+the headline, the `--rows-extra` workloads and every rank's per-kernel times.  --no-extras / --no-cpu-baseline trim a --full run.
+
+N > 1 (launched by torch.distributed.run, one rank per GPU), the --shard mode timed (both with --full):
   rows   (the headline, north_star's partitioning: "rays shard across the GPUs of one node with an RCCL all-gather of rendered tiles";
          strong scaling): ONE frame, contiguous bundle-map row strips over the ranks, every rank prepares (strip-only plan,
          gdb_prepare_rows) and renders its strip straight into the packed (n_bundles, 41) buffer, a single RCCL
-         all_gather_into_tensor of the strips; per rank `prepare_ms`, `kernel_ms`, `allgather_ms` and bus GB/s are reported and the
-         gathered strips are checked bit for bit against a full render.  The same protocol on c4 and c5 (the
-         meaningful multi-GPU points; a 512x640 frame is ~0.1 ms of work and its split is bound by the gather's latency) rides in
-         the line as `rows_c4` / `rows_c5`.
+         all_gather_into_tensor of the strips.  --full: per rank `prepare_ms`, `kernel_ms`, `allgather_ms` and bus GB/s are
+         reported and the gathered strips are checked bit for bit against a full render; the same protocol on c4 and c5 (SURVEY
+         8(e): the meaningful multi-GPU points; a 512x640 frame is ~0.1 ms of work and its split is bound by the gather's latency)
+         rides in the line as `rows_c4` / `rows_c5`.
   frames (the `independent_frames` record, weak scaling): every rank renders its own frame (independent target views, as an
          evaluation sweep does), no data-path collective; `--shard frames` makes it the headline.
 
@@ -421,14 +425,17 @@ def main():
     ap.add_argument("--schedule", type=int, default=0, choices=[0, 1, 2, 3, 4], help="GDB_SCHED_*: 0 auto, 1 slot waves, 2 segment wave, 3 dense, 4 flat")
     ap.add_argument("--path", default="fused", choices=["fused", "unfused"])
     ap.add_argument("--shard", default="rows", choices=["rows", "frames"], help="N > 1: which mode is the headline (both are timed); rows = north_star's partitioning")
-    ap.add_argument("--rows-extra", default="c4,c5", help="N > 1: workloads whose rows-mode record rides in the line beside the headline ('' = none)")
+    ap.add_argument("--rows-extra", default="c4,c5", help="N > 1, --full: workloads whose rows-mode record rides in the line beside the headline ('' = none)")
     ap.add_argument("--frame-ring", type=int, default=0,
                     help="number of distinct device copies of the input frame the steps cycle through (0 = as many as it takes to "
                          "exceed the 256 MiB Infinity Cache, at most 8): consecutive steps then read their inputs from HBM, not from cache")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary-precision record, PSNR, measured peaks and t_frame")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: roofline and per-kernel times, "
+                         "other precisions / sizes / modes, parity, measured peaks, t_frame, the CPU baseline (off: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary-precision record, PSNR, measured peaks and t_frame")
     ap.add_argument("--sources-ready-record", action="store_true",
-                    help="with --no-extras: still time the `prepare_sources_ready` record (a sweep of target views over fixed source views)")
+                    help="with --full --no-extras: still time the `prepare_sources_ready` record (a sweep of target views over fixed source views)")
     ap.add_argument("--streams", type=int, default=1,
                     help="fused path, N = 1 only: render consecutive (independent) frames on this many HIP streams with their own "
                          "workspaces, so one frame's fill/drain overlaps the next; per-launch durations then overlap too (default 1)")
@@ -590,8 +597,8 @@ def main():
     def rows_record(wl_name, wl_, frame_np_, steps, warmup, eng_=None, pname_=None, keep=None):
         """north_star's partitioning of ONE frame of workload `wl_name` over the ranks: contiguous bundle-map row strips; every rank
         prepares (whole pyramid, strip-only plan), renders its strip straight into the packed buffer and ONE all-gather leaves all rows
-        on every rank.  Returns the record (rank-0 view + every rank's prepare / kernel / all-gather times); `keep` (a dict) receives
-        the gathered outputs of the last timed step."""
+        on every rank.  Returns the record (rank-0 view; --full: + every rank's prepare / kernel / all-gather times and the check of
+        the gathered strips); `keep` (a dict) receives the gathered outputs of the last timed step."""
         Ho_, Wo_ = wl_["Ho"], wl_["Wo"]
         H_, W_ = Ho_ // 2, Wo_ // 2
         fr = to_dev(frame_np_, dev)
@@ -627,6 +634,14 @@ def main():
         dt_ = timed.run(step, warmup, steps)
         if keep is not None:  # the packed rows [bundle_feat | depth | opacity]
             keep.update(bundle_feat=g.full[:, :e.Q].clone(), bundle_depth=g.full[:, e.Q].clone(), bundle_opacity=g.full[:, e.Q + 1].clone())
+        rec = {"workload": wl_name, "mode": "rows: one frame, row strips, strip-only plan, packed output, one all-gather", "scaling": "strong",
+               "value": Ho_ * Wo_ * steps / dt_, "unit": "rays/s", "ms_per_step": dt_ / steps * 1e3, "steps": steps, "rays_per_step": Ho_ * Wo_,
+               "allgather_bytes_per_rank": g.nbytes,
+               "collective": "gloo (rehearsal, staged through host memory)" if rehearse else "RCCL all_gather_into_tensor, in place" if g.even else "RCCL all_gather_into_tensor, padded",
+               "world_size": world, "precision": pname_, "dtype": DTYPE[pname_], "frame_ring": nr}
+        if not args.full:
+            del g, rg, fr
+            return rec, e, (r0_, r1_)
         timed.sample(step)
         # untimed check: the gathered strips equal this rank's own render of the whole frame, bit for bit
         e.prepare(rg[ri[0]])
@@ -638,15 +653,10 @@ def main():
         dist.all_gather_object(per, mine)
         share_ = (r1_ - r0_) / H_
         af_ = alg_flops(n_s, wl_["V"]) * share_
-        rec = {"workload": wl_name, "mode": "rows: one frame, row strips, strip-only plan, packed output, one all-gather", "scaling": "strong",
-               "value": Ho_ * Wo_ * steps / dt_, "unit": "rays/s", "ms_per_step": dt_ / steps * 1e3, "steps": steps, "rays_per_step": Ho_ * Wo_,
-               "prepare_ms": mine["prepare_ms"], "kernel_ms": mine["kernel_ms"], "allgather_ms": mine["allgather_ms"],
-               "allgather_bytes_per_rank": g.nbytes, "bus_GBps": mine["bus_GBps"],
-               "collective": "gloo (rehearsal, staged through host memory)" if rehearse else "RCCL all_gather_into_tensor, in place" if g.even else "RCCL all_gather_into_tensor, padded",
-               "world_size": world, "gathered_equals_full_render": all(p["gathered_equals_full_render"] for p in per),
-               "kernel": e.render_info(None, r0_, r1_)["kernel"], "strip_mfma_frac": (af_ / (mine["kernel_ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[pname_]) if mine["kernel_ms"] else None,
-               "precision": pname_, "dtype": DTYPE[pname_],
-               "n_samples": n_s, "frame_ring": nr, "per_rank": per}
+        rec.update({"prepare_ms": mine["prepare_ms"], "kernel_ms": mine["kernel_ms"], "allgather_ms": mine["allgather_ms"], "bus_GBps": mine["bus_GBps"],
+                    "gathered_equals_full_render": all(p["gathered_equals_full_render"] for p in per),
+                    "kernel": e.render_info(None, r0_, r1_)["kernel"], "strip_mfma_frac": (af_ / (mine["kernel_ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[pname_]) if mine["kernel_ms"] else None,
+                    "n_samples": n_s, "per_rank": per})
         del g, rg, fr
         return rec, e, (r0_, r1_)
 
@@ -656,36 +666,40 @@ def main():
 
     rows_mode = world > 1 and args.shard == "rows"
     extra = {}
-    kern_fused_ms = kern_warm_ms = None
+    kern_fused_ms = kern_warm_ms = kern_ms = None
     r0, r1 = 0, H
     if world == 1:
         dt = timed.run(step_frame, args.warmup, args.steps)
         if args.dump_outputs:
             last.update(step_outputs())
-        if args.path == "fused" and args.streams == 1:
+        if args.full and args.path == "fused" and args.streams == 1:
             kern_warm_ms = hot_ms(timed, lambda: eng.render(0, H, None, out))
             kern_fused_ms = ring_kernel_ms() if len(ring) > 1 else kern_warm_ms
             eng.prepare(frame)
-        else:
+        elif args.full:
             timed.sample(step_frame)
         rays_per_step, share = Ho * Wo, 1.0
     else:
-        # both modes are timed; --shard picks the headline
-        rec_rows, _, (r0, r1) = rows_record(args.workload, wl, frame_np, args.steps, args.warmup, eng,
-                                            keep=last if args.dump_outputs and args.shard == "rows" else None)
-        # frames mode: every rank its own frame (seeded by rank)
-        frame = to_dev(synthetic.make_frame(Ho, Wo, V=V, scene=wl["scene"], seed=rank), dev)
-        ring[:] = [frame] + [{k: v.clone() for k, v in frame.items()} for _ in range(nring - 1)]
-        kern_pairs.clear()
-        dt_frames = timed.run(step_frame, args.warmup, args.steps)
-        if args.dump_outputs and args.shard == "frames":
-            last.update(step_outputs())
-        timed.sample(step_frame)
-        kern_frames = ev_ms(kern_pairs)
-        rec_frames = {"mode": "frames: every rank its own frame, no data-path collective", "scaling": "weak",
-                      "value": world * Ho * Wo * args.steps / dt_frames, "ms_per_step": dt_frames / args.steps * 1e3, "kernel_ms": kern_frames}
+        # --shard picks the headline, the one mode a plain run times; --full times both
+        if rows_mode or args.full:
+            rec_rows, _, (r0, r1) = rows_record(args.workload, wl, frame_np, args.steps, args.warmup, eng,
+                                                keep=last if args.dump_outputs and args.shard == "rows" else None)
+        if not rows_mode or args.full:
+            # frames mode: every rank its own frame (seeded by rank)
+            frame = to_dev(synthetic.make_frame(Ho, Wo, V=V, scene=wl["scene"], seed=rank), dev)
+            ring[:] = [frame] + [{k: v.clone() for k, v in frame.items()} for _ in range(nring - 1)]
+            kern_pairs.clear()
+            dt_frames = timed.run(step_frame, args.warmup, args.steps)
+            if args.dump_outputs and args.shard == "frames":
+                last.update(step_outputs())
+            kern_frames = None
+            if args.full:
+                timed.sample(step_frame)
+                kern_frames = ev_ms(kern_pairs)
+            rec_frames = {"mode": "frames: every rank its own frame, no data-path collective", "scaling": "weak",
+                          "value": world * Ho * Wo * args.steps / dt_frames, "ms_per_step": dt_frames / args.steps * 1e3, "kernel_ms": kern_frames}
         # the same rows protocol on the workloads SURVEY 8(e) names as the meaningful multi-GPU points (shorter regions)
-        for name in [x for x in args.rows_extra.split(",") if x and x != args.workload and not (args.smax or args.sampling != "config")]:
+        for name in [x for x in args.rows_extra.split(",") if args.full and x and x != args.workload and not (args.smax or args.sampling != "config")]:
             try:
                 w2 = dict(WORKLOADS[name])
                 k2 = max(20, min(args.steps, 200 if name != "c5" else 60))
@@ -696,71 +710,28 @@ def main():
         if rows_mode:
             dt, rays_per_step, share = rec_rows["ms_per_step"] * 1e-3 * args.steps, Ho * Wo, (r1 - r0) / H
             extra.update({k: rec_rows[k] for k in ("prepare_ms", "allgather_ms", "allgather_bytes_per_rank", "bus_GBps", "collective", "world_size",
-                                                   "gathered_equals_full_render", "mode")})
-            extra["rows_per_rank"] = rec_rows["per_rank"]
-            extra["independent_frames"] = rec_frames
-            # both figures under names that do not depend on which mode is the headline (a stable key across rounds)
-            extra["value_strong_rows"] = rec_rows["value"]; extra["value_weak_frames"] = rec_frames["value"]
-            kern_ms_override = rec_rows["kernel_ms"]
+                                                   "gathered_equals_full_render", "mode") if k in rec_rows})
+            if args.full:
+                extra["rows_per_rank"] = rec_rows["per_rank"]
+                extra["independent_frames"] = rec_frames
+                # both figures under names that do not depend on which mode is the headline (a stable key across rounds)
+                extra["value_strong_rows"] = rec_rows["value"]; extra["value_weak_frames"] = rec_frames["value"]
+                kern_ms = rec_rows["kernel_ms"]
         else:
             dt, rays_per_step, share = dt_frames, world * Ho * Wo, 1.0
-            extra["single_frame_rows"] = rec_rows
-            extra["value_strong_rows"] = rec_rows["value"]; extra["value_weak_frames"] = rec_frames["value"]
-            extra.update({"world_size": world, "gathered_equals_full_render": rec_rows["gathered_equals_full_render"]})
-            kern_ms_override = kern_frames
+            extra["world_size"] = world
+            if args.full:
+                extra["single_frame_rows"] = rec_rows
+                extra["value_strong_rows"] = rec_rows["value"]; extra["value_weak_frames"] = rec_frames["value"]
+                extra["gathered_equals_full_render"] = rec_rows["gathered_equals_full_render"]
+                kern_ms = kern_frames
         eng.prepare(frame)
 
-    kern_ms = (kern_fused_ms if kern_fused_ms is not None else ev_ms(kern_pairs)) if world == 1 else kern_ms_override
+    if world == 1:
+        kern_ms = kern_fused_ms if kern_fused_ms is not None else ev_ms(kern_pairs)
     ms_per_step = dt / args.steps * 1e3
     value = rays_per_step * args.steps / dt
-
-    # ---- roofline of the dominant kernel (per launch, this rank) -------------------------------------------------------
-    n_samples = int(eng.sample()["total"].item())  # actual adaptive sample count of the frame (operator mirror, untimed)
-    ab = alg_bytes(Ho, Wo, V) * share
-    af = alg_flops(n_samples, V) * share
-    if args.path == "fused":
-        kname = eng.render_info(prec, r0, r1)["kernel"]   # the library's own answer (gdb_render_info): no copy of GDB_SCHED_AUTO's rule here
-    else:
-        kname = "k_mlp"
-        ab = 4.0 * n_samples * (V * eng.P + 8 + 1 + eng.Q) + 4 * 11930  # what that kernel must read + write
     pname = args.precision if args.path == "fused" else "f32"
-    hbm_gbs = ab / (kern_ms * 1e-3) / 1e9
-    mfma_tf = af / (kern_ms * 1e-3) / 1e12
-    hbm_frac, mfma_frac = hbm_gbs / HBM_PEAK_GBS, mfma_tf / MFMA_PEAK_TFLOPS[pname]
-    traffic, tsrc = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        # PMC numbers can only be collected under rocprofv3 (tools/profile_round.sh), so they are static between profile runs: the
-        # file records the sha256 of the kernel source it was measured on, and a number measured on another source is refused
-        try:
-            tj = json.load(open(tpath))
-            src_sha = kernel_source_sha16()
-            if tj.get("_kernel_source_sha256_16") == src_sha:
-                tkey = f"{args.workload}:{kname}:{pname}"
-                traffic = tj.get(tkey)
-                # the file a key's counters were read from (per key since round 6: one generic string named files of OTHER workloads)
-                tsrc = (tj.get("_sources", {}).get(tkey) or tj.get("_source")) if traffic is not None else f"profiles/traffic.json holds no entry for {tkey}"
-            else:
-                tsrc = f"profiles/traffic.json was measured on other kernel sources ({tj.get('_kernel_source_sha256_16')} != {src_sha}): refused"
-        except Exception:
-            traffic = None
-    # Which roofline bounds the kernel: the larger of the two floors.  At fp32 the MLP's algorithmic flops
-    # against the 157 TFLOP/s fp32 matrix peak is the longer floor (c2: 74 us vs 9 us of HBM time); with f16 operands
-    # (2.5 PFLOP/s) the HBM floor is.
-    if args.path == "fused" and mfma_frac >= hbm_frac:
-        roof = {"bound": "mfma", "kernel": kname, "achieved": mfma_tf, "peak": MFMA_PEAK_TFLOPS[pname], "unit": "TFLOP/s", "frac": mfma_frac}
-    else:
-        roof = {"bound": "hbm", "kernel": kname, "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_frac}
-    roof.update({"traffic": traffic, "traffic_source": tsrc, "kernel_ms": kern_ms, "alg_bytes": ab, "alg_flops": af, "n_samples": n_samples,
-                 "kernel_ms_cache_warm": kern_warm_ms,
-                 "kernel_samples": 200 if kern_fused_ms is not None else (len(kern_pairs) if world == 1 else 40),
-                 "kernel_ms_how": "HBM ring" if (kern_fused_ms is not None and len(ring) > 1) else "one resident frame" if kern_fused_ms is not None else "event pairs on sampled steps",
-                 "note": "achieved = ALGORITHMIC bytes / flops (SURVEY.md §8(d)) per frame / kernel_ms; kernel_ms = GPU time of the render's ONE "
-                         "launch on HBM-cold inputs: one engine (workspace) per ring copy of the frame, each prepared once, then 200 render calls "
-                         "cycling through them between one HIP event pair on the launch stream, untimed, right after the timed region - the "
-                         "kernel and the inputs of the timed region without the prepare launch in between; rocprofv3's average for the same "
-                         "kernel over the timed region is committed under profiles/ and must agree.  kernel_ms_cache_warm = the same on one "
-                         "resident frame.  N > 1: event pairs around the render on 40 sampled steps"})
 
     res = {
         "metric": "rendered rays/sec, GDB-NeRF hot path (sample+fetch+MLP+composite)", "value": value, "unit": "rays/s",
@@ -778,9 +749,57 @@ def main():
                    "timed_region": f"{args.steps} steps over a ring of {nring} distinct HBM copies of the frame "
                                    f"({nring * in_bytes / 1e6:.0f} MB > the 256 MiB Infinity Cache): each copy is read {args.steps / nring:.1f} times, "
                                    f"never twice in a row"},
-        "t_hot_ms": ms_per_step, "hbm_frac": hbm_frac, "mfma_frac": mfma_frac,
-        "roofline": roof,
+        "t_hot_ms": ms_per_step,
     }
+
+    if args.full:
+        # ---- roofline of the dominant kernel (per launch, this rank) ---------------------------------------------------
+        n_samples = int(eng.sample()["total"].item())  # actual adaptive sample count of the frame (operator mirror, untimed)
+        ab = alg_bytes(Ho, Wo, V) * share
+        af = alg_flops(n_samples, V) * share
+        if args.path == "fused":
+            kname = eng.render_info(prec, r0, r1)["kernel"]   # the library's own answer (gdb_render_info): no copy of GDB_SCHED_AUTO's rule here
+        else:
+            kname = "k_mlp"
+            ab = 4.0 * n_samples * (V * eng.P + 8 + 1 + eng.Q) + 4 * 11930  # what that kernel must read + write
+        hbm_gbs = ab / (kern_ms * 1e-3) / 1e9
+        mfma_tf = af / (kern_ms * 1e-3) / 1e12
+        hbm_frac, mfma_frac = hbm_gbs / HBM_PEAK_GBS, mfma_tf / MFMA_PEAK_TFLOPS[pname]
+        traffic, tsrc = None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath):
+            # PMC numbers can only be collected under rocprofv3 (tools/profile_round.sh), so they are static between profile runs: the
+            # file records the sha256 of the kernel source it was measured on, and a number measured on another source is refused
+            try:
+                tj = json.load(open(tpath))
+                src_sha = kernel_source_sha16()
+                if tj.get("_kernel_source_sha256_16") == src_sha:
+                    tkey = f"{args.workload}:{kname}:{pname}"
+                    traffic = tj.get(tkey)
+                    # the file a key's counters were read from (per key since round 6: one generic string named files of OTHER workloads)
+                    tsrc = (tj.get("_sources", {}).get(tkey) or tj.get("_source")) if traffic is not None else f"profiles/traffic.json holds no entry for {tkey}"
+                else:
+                    tsrc = f"profiles/traffic.json was measured on other kernel sources ({tj.get('_kernel_source_sha256_16')} != {src_sha}): refused"
+            except Exception:
+                traffic = None
+        # Which roofline bounds the kernel: the larger of the two floors.  At fp32 the MLP's algorithmic flops
+        # against the 157 TFLOP/s fp32 matrix peak is the longer floor (c2: 74 us vs 9 us of HBM time); with f16 operands
+        # (2.5 PFLOP/s) the HBM floor is.
+        if args.path == "fused" and mfma_frac >= hbm_frac:
+            roof = {"bound": "mfma", "kernel": kname, "achieved": mfma_tf, "peak": MFMA_PEAK_TFLOPS[pname], "unit": "TFLOP/s", "frac": mfma_frac}
+        else:
+            roof = {"bound": "hbm", "kernel": kname, "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_frac}
+        roof.update({"traffic": traffic, "traffic_source": tsrc, "kernel_ms": kern_ms, "alg_bytes": ab, "alg_flops": af, "n_samples": n_samples,
+                     "kernel_ms_cache_warm": kern_warm_ms,
+                     "kernel_samples": 200 if kern_fused_ms is not None else (len(kern_pairs) if world == 1 else 40),
+                     "kernel_ms_how": "HBM ring" if (kern_fused_ms is not None and len(ring) > 1) else "one resident frame" if kern_fused_ms is not None else "event pairs on sampled steps",
+                     "note": "achieved = ALGORITHMIC bytes / flops (SURVEY.md §8(d)) per frame / kernel_ms; kernel_ms = GPU time of the render's ONE "
+                             "launch on HBM-cold inputs: one engine (workspace) per ring copy of the frame, each prepared once, then 200 render calls "
+                             "cycling through them between one HIP event pair on the launch stream, untimed, right after the timed region - the "
+                             "kernel and the inputs of the timed region without the prepare launch in between; rocprofv3's average for the same "
+                             "kernel over the timed region is committed under profiles/ and must agree.  kernel_ms_cache_warm = the same on one "
+                             "resident frame.  N > 1: event pairs around the render on 40 sampled steps"})
+        res.update({"hbm_frac": hbm_frac, "mfma_frac": mfma_frac, "roofline": roof})
     res.update(extra)
 
     def sources_ready_record(pname_, k2_):
@@ -814,11 +833,11 @@ def main():
                 "note": "step = gdb_prepare_ex(GDB_PREP_SOURCES_READY) + render: camera block and plan rebuilt, pyramids / image copy of the "
                         "fixed source views kept; never the headline (its step prepares in full)"}
 
-    if rank == 0 and world == 1 and args.no_extras and args.sources_ready_record and args.path == "fused" and args.streams == 1:
+    if rank == 0 and world == 1 and args.full and args.no_extras and args.sources_ready_record and args.path == "fused" and args.streams == 1:
         res["prepare_sources_ready"] = sources_ready_record(args.precision, max(100, min(args.steps, 1000)))
         eng.prepare(frame)
 
-    if rank == 0 and world == 1 and not args.no_extras and args.path == "fused" and args.streams == 1:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and args.path == "fused" and args.streams == 1:
         # Parity in the line itself, against the CPU ORACLE (oracle/gdb_oracle.py, the checker of tests/): the c1-size frame (64x80, BASELINE
         # configs[0]: a frame the oracle finishes in a second) rendered by this build at the headline precision - PSNR delta of the fine
         # RGB (north_star: within 0.05 dB) and max |bundle_feat - oracle|.  The benched frame itself is compared with the library's
@@ -993,13 +1012,14 @@ def main():
             res["t_frame_ms"] = None
             res["t_frame_error"] = repr(ex)
     if dist is not None:
-        # every rank's dominant-kernel time and roofline fraction ride in rank 0's line (the line's `roofline` is rank 0's own)
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, {"rank": rank, "rows": [r0, r1], "kernel_ms": kern_ms, "roofline_frac": roof["frac"],
-                                          "bound": roof["bound"], "hbm_frac": hbm_frac, "mfma_frac": mfma_frac})
-        res["per_rank"] = per_rank
+        if args.full:
+            # every rank's dominant-kernel time and roofline fraction ride in rank 0's line (the line's `roofline` is rank 0's own)
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, {"rank": rank, "rows": [r0, r1], "kernel_ms": kern_ms, "roofline_frac": roof["frac"],
+                                              "bound": roof["bound"], "hbm_frac": hbm_frac, "mfma_frac": mfma_frac})
+            res["per_rank"] = per_rank
         dist.destroy_process_group()
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # N > 1: the 8-thread row only, on rank 0, after the process group is gone (no rank waits on it)
         res["cpu_baseline"] = cpu_baseline(wl, frame_np, weights_np, quick=world > 1)
     if rank == 0 and args.dump_outputs:

@@ -74,8 +74,41 @@ def test_bench_dump_of_the_gathered_row_strips_equals_one_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GDB_BENCH_REHEARSE="1")
     _bench([], tmp_path / "one")
-    rec = _bench(["--gpus", "2", "--rows-extra", ""], tmp_path / "two", env)
+    rec = _bench(["--gpus", "2", "--rows-extra", "", "--full"], tmp_path / "two", env)
     assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["gathered_equals_full_render"] is True
     for name in ("bundle_feat", "bundle_depth", "bundle_opacity"):
         np.testing.assert_allclose(np.load(tmp_path / "two" / f"{name}.npy"), np.load(tmp_path / "one" / f"{name}.npy"), rtol=0, atol=1e-5,
                                    err_msg=name)
+
+
+@pytest.mark.gpu
+def test_plain_run_carries_the_headline_alone_and_full_adds_the_rest(tmp_path):
+    """A plain run times its steps and prints the headline, none of what `--full` measures after them; `--full` (trimmed by
+    --no-extras / --no-cpu-baseline) adds the roofline of the dominant kernel, timed in runs of its own."""
+    plain = _bench([], tmp_path / "plain")
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["unit"] == "rays/s" and plain["higher_is_better"] is True
+    assert plain["dtype"] == "f32" and plain["steps"] == 3 and plain["warmup"] == 1
+    assert not set(plain) & {"roofline", "hbm_frac", "mfma_frac", "secondary", "psnr_delta_db", "peaks_measured", "t_frame_ms", "cpu_baseline"}
+    full = _bench(["--full"], tmp_path / "full")
+    assert full["dtype"] == plain["dtype"] and full["roofline"]["kernel_ms"] > 0 and 0 < full["mfma_frac"] < 1
+    for name in ("bundle_feat", "bundle_depth", "bundle_opacity"):
+        np.testing.assert_allclose(np.load(tmp_path / "full" / f"{name}.npy"), np.load(tmp_path / "plain" / f"{name}.npy"), rtol=0, atol=1e-5,
+                                   err_msg=name)
+
+
+@pytest.mark.gpu
+def test_plain_two_rank_run_times_its_shard_mode_alone(tmp_path):
+    """N = 2 (two ranks sharing the card, GDB_BENCH_REHEARSE=1) without --full: only the --shard mode is timed, none of the other
+    mode, the --rows-extra workloads or the per-rank figures; what each mode dumps is still the N = 1 render (rank 0's frame)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(GDB_BENCH_REHEARSE="1")
+    _bench([], tmp_path / "one")
+    only_full = {"independent_frames", "single_frame_rows", "rows_c4", "rows_c5", "rows_per_rank", "per_rank", "gathered_equals_full_render",
+                 "value_strong_rows", "value_weak_frames", "roofline", "cpu_baseline"}
+    for shard, scaling in (("rows", "strong"), ("frames", "weak")):
+        rec = _bench(["--gpus", "2", "--shard", shard], tmp_path / shard, env)
+        assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["scaling"] == scaling and rec["value"] > 0 and rec["ms_per_step"] > 0, shard
+        assert not set(rec) & only_full, (shard, set(rec) & only_full)
+        for name in ("bundle_feat", "bundle_depth", "bundle_opacity"):
+            np.testing.assert_allclose(np.load(tmp_path / shard / f"{name}.npy"), np.load(tmp_path / "one" / f"{name}.npy"), rtol=0, atol=1e-5,
+                                       err_msg=f"{shard} {name}")

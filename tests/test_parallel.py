@@ -272,7 +272,7 @@ def test_bench_two_ranks_self_launched_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GDB_BENCH_REHEARSE="1")
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--prewarm-ms", "50", "--rows-extra", "c4"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--prewarm-ms", "50", "--rows-extra", "c4", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -292,7 +292,7 @@ def test_bench_two_ranks_self_launched_on_one_gpu():
     assert fr["scaling"] == "weak" and fr["value"] > 0
     assert rec["cpu_baseline"]["cores"] == 8 and rec["cpu_baseline"]["value"] > 0
     # ... and `--shard frames` puts the weak-scaling record on top
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--prewarm-ms", "50", "--shard", "frames", "--no-cpu-baseline", "--rows-extra", ""],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--prewarm-ms", "50", "--shard", "frames", "--full", "--no-cpu-baseline", "--rows-extra", ""],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     rec2 = json.loads([l for l in p.stdout.splitlines() if l.strip()][0])

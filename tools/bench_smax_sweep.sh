@@ -8,6 +8,6 @@ first=1
 for S in 3 6 8; do for M in adaptive fixed; do for P in f32 f32x f16; do
   [ $first = 1 ] || echo ","
   first=0
-  python3 $ROOT/bench.py --no-cpu-baseline --no-extras --workload c2 --smax $S --sampling $M --precision $P --steps ${BENCH_STEPS:-300} --warmup 50 2>/dev/null
+  python3 $ROOT/bench.py --full --no-cpu-baseline --no-extras --workload c2 --smax $S --sampling $M --precision $P --steps ${BENCH_STEPS:-300} --warmup 50 2>/dev/null
 done; done; done
 echo "]"

@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for P in ${PRECS:-f32 f32x f16}; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$P -- python3 $ROOT/bench.py --no-cpu-baseline --no-extras --workload $WL --precision $P > $OUT/bench_under_trace_$P.json 2> $OUT/trace_$P.log
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$P -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-extras --workload $WL --precision $P > $OUT/bench_under_trace_$P.json 2> $OUT/trace_$P.log
   bash $ROOT/tools/prof_pmc.sh $TAG/pmc_$P --workload $WL --precision $P > $OUT/pmc_$P.log 2>&1
 done
 python3 - <<PY

@@ -8,6 +8,6 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$ROOT/gpurun_out/valu_split; mkdir -p $OUT
 export GDB_NERF_LIB=$ROOT/gdb-nerf_amd/libgdbnerf_hip.skip.so
 cd /tmp; export TMPDIR=/tmp
 for sk in 0 7 8 15; do
-  GDB_FUSED_SKIP=$sk timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY --kernel-trace --output-format csv -d $OUT/skip$sk -- python3 $ROOT/bench.py --no-cpu-baseline --no-extras --steps 5 --warmup 1 --prewarm-ms 0 "$@" > /dev/null 2>&1
+  GDB_FUSED_SKIP=$sk timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY --kernel-trace --output-format csv -d $OUT/skip$sk -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-extras --steps 5 --warmup 1 --prewarm-ms 0 "$@" > /dev/null 2>&1
   echo "skip=$sk"; python3 $ROOT/tools/pmc_summary.py $OUT/skip$sk 2>/dev/null | grep -A9 k_render_fused | grep -v "=="
 done
