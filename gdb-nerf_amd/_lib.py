@@ -85,6 +85,10 @@ _SIGNATURES = {
     "gdb_decode_rows": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
     "gdb_merge_packed_rows": (C.c_int, [_CFG, _FRM, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gdb_upsample_maps": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, _P, _P]),
+    "gdb_cost_reg_packed_floats": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_size_t)]),
+    "gdb_pack_cost_reg_weights": (C.c_int, [C.c_int32] * 4 + [C.POINTER(_P), _P]),
+    "gdb_cost_reg_workspace_bytes": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_size_t)]),
+    "gdb_cost_reg": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 4 + [_P, _P, C.c_size_t, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

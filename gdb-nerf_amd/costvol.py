@@ -1,9 +1,11 @@
 """Torch-facing wrappers of the two "next"-row kernels: the plane-sweep cost volume
 and the depth regression of the cascade MVS stage, same signatures as the reference functions
-(networks/gdb_nerf/depth_net.py:424-514).  CUDA tensors only — there is no CPU fallback here either."""
+(networks/gdb_nerf/depth_net.py:424-514), and `CostReg`, the HIP forward of the cascade's cost-regularisation 3-D U-Nets
+(networks/gdb_nerf/cost_reg_net.py).  CUDA tensors only — there is no CPU fallback here either."""
 import ctypes as C
 from typing import Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -49,3 +51,69 @@ def depth_regression(depth_values, depth_prob, ci_scale: float, inv_depth: bool)
     _lib.check(lib.gdb_depth_regression(dv.data_ptr(), pr.data_ptr(), B, D, H, W, C.c_float(float(ci_scale)), int(bool(inv_depth)),
                                         depth.data_ptr(), ci.data_ptr(), torch.cuda.current_stream(dv.device).cuda_stream))
     return depth, ci
+
+
+def cost_reg_keys(depth: int):
+    """State-dict keys of a `_UNet3d` in the order gdb_pack_cost_reg_weights takes them (include/gdb_nerf_hip.h); eps follows."""
+    keys = []
+    for i in range(3 * depth + 1):
+        keys += [f"conv{i}.0.weight", f"conv{i}.1.weight", f"conv{i}.1.bias", f"conv{i}.1.running_mean", f"conv{i}.1.running_var"]
+    return keys + ["feat_head.weight", "prob_head.weight"]
+
+
+class CostReg:
+    """Eval-mode forward of a `_UNet3d` (cost_reg_net.py:24-54) on the HIP library: `CostReg(module)(cost)` returns
+    (volume (B, out, D, H, W), prob (B, D, H, W)) like `module(cost)`, on the current stream.  The module's parameters and
+    buffers are packed on the host and uploaded once, and again whenever any of them changes storage or version (running
+    statistics included: they are buffers, not parameters); an in-place write through `.data` needs `invalidate()`."""
+
+    def __init__(self, module: torch.nn.Module) -> None:
+        self.module = module
+        self.depth = int(module._depth)
+        self.cin, self.c = int(module.conv0[0].in_channels), int(module.conv0[0].out_channels)
+        self.cout = int(module.feat_head.out_channels)
+        eps = {float(m.eps) for m in module.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)}
+        if len(eps) != 1:
+            raise ValueError(f"the U-Net's batch norms use different eps {sorted(eps)}; the packed form holds one")
+        self.eps = eps.pop()
+        self._key, self.packed = None, None
+
+    def invalidate(self) -> None:
+        self._key = None
+
+    def _versions(self):
+        return tuple((t.data_ptr(), t._version) for t in (*self.module.parameters(), *self.module.buffers()))
+
+    def pack(self, device) -> torch.Tensor:
+        key = (torch.device(device), self._versions())
+        if key == self._key:
+            return self.packed
+        lib = _lib.load()
+        sd = self.module.state_dict()
+        keys = cost_reg_keys(self.depth)
+        arrs = [np.ascontiguousarray(sd[k].detach().cpu().numpy(), dtype=np.float32) for k in keys]
+        arrs.append(np.array([self.eps], dtype=np.float32))
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        n = C.c_size_t()
+        _lib.check(lib.gdb_cost_reg_packed_floats(self.depth, self.cin, self.c, self.cout, C.byref(n)))
+        host = np.zeros(n.value, dtype=np.float32)
+        _lib.check(lib.gdb_pack_cost_reg_weights(self.depth, self.cin, self.c, self.cout, ptrs, host.ctypes.data))
+        self.packed, self._key = torch.from_numpy(host).to(device), key
+        return self.packed
+
+    def __call__(self, cost: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        lib = _lib.load()
+        cost = _c(cost, "cost")
+        if cost.dim() != 5 or cost.shape[1] != self.cin:
+            raise ValueError(f"cost volume of shape {tuple(cost.shape)}, expected (B, {self.cin}, D, H, W)")
+        B, _, D, H, W = cost.shape
+        packed = self.pack(cost.device)
+        nbytes = C.c_size_t()
+        _lib.check(lib.gdb_cost_reg_workspace_bytes(self.depth, self.cin, self.c, self.cout, B, D, H, W, C.byref(nbytes)))
+        # allocated per call: torch's caching allocator hands the block back without a device allocation and keeps it stream-safe
+        ws = torch.empty(((nbytes.value + 3) // 4,), device=cost.device)
+        volume = torch.empty((B, self.cout, D, H, W), device=cost.device)
+        prob = torch.empty((B, D, H, W), device=cost.device)
+        _lib.check(lib.gdb_cost_reg(self.depth, self.cin, self.c, self.cout, cost.data_ptr(), B, D, H, W, packed.data_ptr(), ws.data_ptr(),
+                                    nbytes.value, volume.data_ptr(), prob.data_ptr(), torch.cuda.current_stream(cost.device).cuda_stream))
+        return volume, prob

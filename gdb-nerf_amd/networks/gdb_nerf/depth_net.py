@@ -96,12 +96,33 @@ class DepthNet(nn.Module):
         self.num_depth = list(mvs.num_depth)
         self.inv_depth = list(mvs.inv_depth)
         self.hip_cost_volume = bool(getattr(mvs, "hip_cost_volume", True))
+        # the 3-D U-Nets on the HIP library (costvol.CostReg): eval mode and fp32 CUDA input only; off by default
+        self.hip_cost_reg = bool(getattr(mvs, "hip_cost_reg", False))
+        self._hip_regs = {}   # stage -> costvol.CostReg (not a module: no state-dict keys)
         # the reference indexes feat_dims by the pyramid level again (depth_net.py:32-37); kept for key/shape parity
         nets = [CostRegNet_small(self.feat_dims[self.vol_levels[0]], mvs.voxel_dim, fpn.base_channels)]
         nets += [CostRegNet(self.feat_dims[self.vol_levels[i]], mvs.voxel_dim, fpn.base_channels) for i in range(1, self.num_stages)]
         self.cost_regs = nn.ModuleList(nets)
         self.nerfs = nn.ModuleList(_AuxStageNerf(config.nerf.nerf_hidden_dims, mvs.voxel_dim, self.feat_dims[i], config.nerf.viewdir_agg)
                                    for i in range(self.num_stages - 1))
+
+    def use_hip_cost_reg(self, feats) -> bool:
+        """The HIP U-Net needs the switch, eval mode (training needs batch statistics and autograd) and fp32 CUDA tensors."""
+        return self.hip_cost_reg and not self.training and _use_hip(feats, True)
+
+    def _cost_reg(self, s: int, cost: torch.Tensor, feats: torch.Tensor):
+        if not self.use_hip_cost_reg(feats):
+            return self.cost_regs[s](cost)
+        from ... import costvol
+        reg = self._hip_regs.get(s)
+        if reg is None or reg.module is not self.cost_regs[s]:
+            reg = self._hip_regs[s] = costvol.CostReg(self.cost_regs[s])
+        return reg(cost)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        for reg in self._hip_regs.values():
+            reg.invalidate()
+        super()._load_from_state_dict(*args, **kwargs)
 
     def forward(self, src_images, ms_feats: List[torch.Tensor], src_exts, src_ints, tar_exts, tar_ints, near_far):
         """Returns (depths, depth_ranges, vol_ranges, feat_volumes, rgb_predictions) per stage like the
@@ -121,11 +142,11 @@ class DepthNet(nn.Module):
                 from ... import costvol
                 hyp = hyp.contiguous()
                 cost = costvol.build_feature_volume(feats, src_exts, K_src, tar_exts, K_tar, hyp, self.inv_depth[s])
-                volume, prob = self.cost_regs[s](cost)
+                volume, prob = self._cost_reg(s, cost, feats)
                 depth, search = costvol.depth_regression(hyp, prob, self.ci_scales[s], self.inv_depth[s])
             else:
                 cost = build_feature_volume(feats, src_exts, K_src, tar_exts, K_tar, hyp, self.inv_depth[s])
-                volume, prob = self.cost_regs[s](cost)
+                volume, prob = self._cost_reg(s, cost, feats)
                 depth, search = depth_regression(hyp, prob, self.ci_scales[s], self.inv_depth[s])
             depths.append(depth.squeeze(1))
             ranges.append(search)

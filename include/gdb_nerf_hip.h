@@ -433,6 +433,31 @@ int gdb_decode_rows(const GdbConfig* cfg, const GdbFrame* shape, const float* d_
                     const float* d_packed_decoder_weights, int32_t num_layers, int32_t precision, int32_t row_begin, int32_t row_end,
                     int32_t phase, void* d_workspace, size_t workspace_bytes, float* d_rgb_c, void* stream);
 
+/* ---- the cascade's cost-regularisation 3-D U-Nets (ABI v7, added) ---------------------------- */
+/* _UNet3d.forward, networks/gdb_nerf/cost_reg_net.py:24-54, eval mode: depth 2 (CostRegNet_small) or 3 (CostRegNet), in_channels cin
+ * (a multiple of 8, <= 256), base_channels (a multiple of 8, base << depth <= 128), out_channels cout = voxel_dim (1 .. 15).  Every
+ * 3x3x3 (transposed) convolution on fp32 MFMA with eval BatchNorm + ReLU (+ the skip add) fused; activations channel-last in the
+ * caller's workspace.
+ *
+ * gdb_pack_cost_reg_weights: h_tensors in this order - for i = 0 .. 3 depth: conv{i}.0.weight, conv{i}.1.weight, conv{i}.1.bias,
+ * conv{i}.1.running_mean, conv{i}.1.running_var; then feat_head.weight, prob_head.weight, and a pointer to the BatchNorm eps (one
+ * float): 5 (3 depth + 1) + 3 host pointers.  Packed layer L (conv0 .. conv{3 depth}, then the heads) holds its weights at
+ * w_off(L) + (((mt T + tap) K + cc) 64 + lane) E + e = weight of GEMM row 16 mt + (lane & 15), input channel ci, tap; T = 27
+ * (tap = (kz 3 + ky) 3 + kx) or 36 for the 8-channel stride-1 layers (rows 8 .. 15 = the same channels one plane further),
+ * ci = 16 cc + 4 e + (lane >> 4) with E = 4 for conv0, else ci = 4 E cc + E (lane >> 4) + e with E = 4 (cin % 16 == 0) or 2; the
+ * heads' rows are feat_head 0 .. cout - 1 and prob_head cout.  A BN layer's weights are followed by [1 / sqrt(var + eps) | mean |
+ * weight | bias] x its cout; each block starts at a multiple of 64 floats.
+ * gdb_cost_reg_workspace_bytes / gdb_cost_reg: d_cost (B, cin, D, H, W) as gdb_build_feature_volume writes it, read in place; D, H
+ * and W divisible by 2^depth (GDB_E_SHAPE otherwise), ws_bytes >= the workspace size (GDB_E_WORKSPACE otherwise; its contents do
+ * not matter).  Out: d_volume (B, cout, D, H, W), d_prob (B, D, H, W) = softmax over D of prob_head.  Every refusal comes before
+ * the first launch.  Deterministic (no atomics). */
+int gdb_cost_reg_packed_floats(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, size_t* out_floats);
+int gdb_pack_cost_reg_weights(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* const* h_tensors, float* h_out);
+int gdb_cost_reg_workspace_bytes(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, int32_t B, int32_t D, int32_t H,
+                                 int32_t W, size_t* out_bytes);
+int gdb_cost_reg(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B, int32_t D, int32_t H,
+                 int32_t W, const float* d_packed, void* d_workspace, size_t ws_bytes, float* d_volume, float* d_prob, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
