@@ -89,6 +89,10 @@ _SIGNATURES = {
     "gdb_pack_cost_reg_weights": (C.c_int, [C.c_int32] * 4 + [C.POINTER(_P), _P]),
     "gdb_cost_reg_workspace_bytes": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_size_t)]),
     "gdb_cost_reg": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 4 + [_P, _P, C.c_size_t, _P, _P, _P]),
+    "gdb_fpn_packed_floats": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_size_t)]),
+    "gdb_pack_fpn_weights": (C.c_int, [C.c_int32] * 4 + [C.POINTER(_P), _P]),
+    "gdb_fpn_workspace_bytes": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_size_t)]),
+    "gdb_fpn": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 3 + [_P, C.c_int32, _P, C.c_size_t, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

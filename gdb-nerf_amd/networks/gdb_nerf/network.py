@@ -26,7 +26,13 @@ class Network(nn.Module):
     def __init__(self, config: SimpleNamespace) -> None:
         super().__init__()
         fpn, mvs, nrf = config.fpn, config.mvs, config.nerf
-        self.feature_net = FeatureNet(base_channels=fpn.base_channels, out_channels=fpn.feat_dims)
+        # fpn.hip_feature_net: the FPN on the HIP library (fpn.FeaturePyramid) in eval mode on fp32 CUDA images; off by default.  A
+        # FeatureNet the library is not built for is refused here, not left to fall back at the first forward.
+        hip_fpn = bool(getattr(fpn, "hip_feature_net", False))
+        if hip_fpn:
+            from ... import fpn as hip_fpn_mod
+            hip_fpn_mod.check_channels(fpn.base_channels, fpn.feat_dims)
+        self.feature_net = FeatureNet(base_channels=fpn.base_channels, out_channels=fpn.feat_dims, hip=hip_fpn)
         self.voxel_dim = mvs.voxel_dim
         self.depth_net = DepthNet(config)
 
@@ -41,6 +47,8 @@ class Network(nn.Module):
 
         # pyramid level whose scale is closest to (not below) the bundle map's 1/b   (reference :40-43)
         self.feat_level = next((i for i, s in enumerate(fpn.feat_scales) if s >= 1.0 / self.b_size), len(fpn.feat_scales))
+        # the pyramid levels a forward reads: the depth net's volume levels and the image-feature level (a hint to the HIP FPN)
+        self.fpn_levels = tuple(sorted(set(mvs.vol_levels) | {self.feat_level}))
         feat_dim = fpn.feat_dims[self.feat_level]
         self.nerf_hidden_dims, self.viewdir_agg = nrf.nerf_hidden_dims, nrf.viewdir_agg
         self.render_scale = 1.0
@@ -220,7 +228,7 @@ class Network(nn.Module):
             src_ints[..., :2, :] *= self.render_scale
             tar_ints[:, :2, :] *= self.render_scale
 
-        ms_feats = [f.unflatten(0, (B, V)) for f in self.feature_net(src_images.flatten(0, 1))]
+        ms_feats = [None if f is None else f.unflatten(0, (B, V)) for f in self.feature_net(src_images.flatten(0, 1), self.fpn_levels)]
         mvs_depths, ranges, vol_ranges, volumes, blend_rgbs = self.depth_net(src_images, ms_feats, src_exts, src_ints, tar_exts, tar_ints, near_far)
         depth_range, vol_range, feat_volume, mvs_depth = ranges[-1], vol_ranges[-1], volumes[-1], mvs_depths[-1]
 

@@ -458,6 +458,39 @@ int gdb_cost_reg_workspace_bytes(int32_t depth, int32_t cin, int32_t base_channe
 int gdb_cost_reg(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B, int32_t D, int32_t H,
                  int32_t W, const float* d_packed, void* d_workspace, size_t ws_bytes, float* d_volume, float* d_prob, void* stream);
 
+/* ---- the feature pyramid network (ABI v7, added) --------------------------------------------------------------------------- */
+/* FeatureNet.forward, networks/gdb_nerf/feature_net.py, eval mode: base_channels c (a multiple of 8, <= 32), out_channels out0, out1,
+ * out2 (multiples of 8, <= 64).  Every convolution on fp32 MFMA with eval BatchNorm + ReLU, or the bias and the upsampled add of the
+ * top-down path, fused; intermediates channel-last in the caller's workspace.
+ *
+ * gdb_pack_fpn_weights: h_tensors in this order - for conv0.0, conv0.1, conv1.0, conv1.1, conv2.0, conv2.1: X.0.weight, X.1.weight,
+ * X.1.bias, X.1.running_mean, X.1.running_var; then out0.weight, out0.bias, inner1.weight, inner1.bias, inner2.weight, inner2.bias,
+ * out1.weight, out2.weight, and a pointer to the BatchNorm eps (one float): 39 host pointers.  Packed layers, in the order conv0.0,
+ * conv0.1, conv1.0, conv1.1, conv2.0, conv2.1, out0, inner1, inner2, out1, out2, hold their weights at
+ * w_off(L) + (((mt T + tap) K + cc) 64 + lane) E + e = weight of GEMM row 16 mt + (lane & 15), with
+ *  - conv0.0 (3 input channels): E = 1, K = 1, T = 7 (9 when c == 8) k-steps; k = 4 tap + (lane >> 4) = (ci R + r) 3 + kx over
+ *    R = 3 (4) input rows r, ky = r - (row >> 3) when c == 8, else ky = r; zeros for k >= 9 R or ky outside 0 .. 2;
+ *  - every other layer: ci = 4 E cc + E (lane >> 4) + e with E = 4 (cin % 16 == 0) or 2, K = cin / (4 E); tap = ky ks + kx (ks = 5
+ *    for conv1.0 / conv2.0, 1 for out0 / inner*, else 3), except for 3x3 layers with 8 output channels: T = 12, tap = r 3 + kx
+ *    over 4 input rows r, ky = r - (row >> 3);
+ *  - GEMM row = output channel, or for the 8-output-channel 3x3 layers row = 8 s + channel with s = the output row y + s; zeros for
+ *    rows >= that count.
+ * Each layer's weights are followed by [1 / sqrt(var + eps) | mean | weight | bias] x its cout (conv blocks) or its bias x cout
+ * (out0, inner1, inner2); out1 and out2 have none; each block starts at a multiple of 64 floats.
+ * gdb_fpn_workspace_bytes / gdb_fpn: d_images (N, 3, H, W), read in place; N, H, W >= 1 (GDB_E_SHAPE otherwise); level_mask: bit l
+ * asks for level l (a non-empty subset of 0 .. 2, GDB_E_BADARG otherwise); ws_bytes >= the workspace size for that mask
+ * (GDB_E_WORKSPACE otherwise; its contents do not matter).  With h = ceil(H / 2), q = ceil(h / 2) (and so for W), out: d_level0
+ * (N, out0, q, wq), d_level1 (N, out1, h, w), d_level2 (N, out2, H, W); a level's pointer may be NULL exactly when the mask leaves
+ * it out.  Only what the mask needs runs: the encoder always, inner1 for levels 1 or 2, inner2 and out2 for level 2.  Every refusal
+ * comes before the first launch.  Deterministic (no atomics). */
+int gdb_fpn_packed_floats(int32_t base_channels, int32_t out0, int32_t out1, int32_t out2, size_t* out_floats);
+int gdb_pack_fpn_weights(int32_t base_channels, int32_t out0, int32_t out1, int32_t out2, const float* const* h_tensors, float* h_out);
+int gdb_fpn_workspace_bytes(int32_t base_channels, int32_t out0, int32_t out1, int32_t out2, int32_t N, int32_t H, int32_t W,
+                            int32_t level_mask, size_t* out_bytes);
+int gdb_fpn(int32_t base_channels, int32_t out0, int32_t out1, int32_t out2, const float* d_images, int32_t N, int32_t H, int32_t W,
+            const float* d_packed, int32_t level_mask, void* d_workspace, size_t ws_bytes, float* d_level0, float* d_level1,
+            float* d_level2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """t_frame: whole Network.forward (CNNs on PyTorch-ROCm + hot path on the HIP library) at DTU eval 512x640, 3 source
 views, random-init weights, the reference's timing protocol (run.py:56-73: synchronise, wall clock, drop the first
-iteration, FPS = 1 / mean).  Prints a JSON object; hot_path in {fused, mirrors}, precision, hip_cost_volume, hip_decoder and
-hip_cost_reg on/off."""
+iteration, FPS = 1 / mean).  Prints a JSON object; hot_path in {fused, mirrors}, precision, hip_cost_volume, hip_decoder,
+hip_cost_reg and hip_feature_net on/off."""
 import json, os, sys, time, numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 from gdb_nerf_amd import synthetic
@@ -15,6 +15,8 @@ batch = {"src_views": {"rgb": t(fr["src_images"]), "extrinsics": t(fr["src_exts"
 res = {}
 for name, opts in {"fused (fp32 MFMA) + hip cost volume + hip decoder [default]": [],
                    "fused (fp32 MFMA) + hip cost volume + hip decoder + hip cost reg": ["mvs.hip_cost_reg", "True"],
+                   "fused (fp32 MFMA) + hip cost volume + hip decoder + hip cost reg + hip feature net": ["mvs.hip_cost_reg", "True",
+                                                                                          "fpn.hip_feature_net", "True"],
                    "split-f16 pairs (fp32-grade) in the fused MLP and the decoder + hip cost volume": ["nerf.precision", "f32x"],
                    "fused + hip cost volume, torch decoder": ["nerf.hip_decoder", "False"],
                    "fused f16 operands + hip cost volume + hip decoder": ["nerf.precision", "f16"],
