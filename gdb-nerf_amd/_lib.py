@@ -25,6 +25,7 @@ PREP_STRIP_WHOLE = 16
 
 GDB_OK, GDB_E_BADARG, GDB_E_SHAPE, GDB_E_HIP, GDB_E_WORKSPACE = 0, -1, -2, -3, -4
 GDB_MAX_SAMPLES, GDB_MAX_MIP, GDB_MAX_VIEWS = 16, 3, 8
+GDB_EVAL_IMAGE_REC, GDB_EVAL_DEPTH_REC = 5, 4
 
 
 class GdbConfig(C.Structure):
@@ -93,6 +94,9 @@ _SIGNATURES = {
     "gdb_pack_fpn_weights": (C.c_int, [C.c_int32] * 4 + [C.POINTER(_P), _P]),
     "gdb_fpn_workspace_bytes": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_size_t)]),
     "gdb_fpn": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 3 + [_P, C.c_int32, _P, C.c_size_t, _P, _P, _P, _P]),
+    "gdb_eval_workspace_bytes": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_size_t)]),
+    "gdb_eval_image": (C.c_int, [_P, _P, _P] + [C.c_int32] * 7 + [_P, C.c_size_t, _P, C.c_int64, _P]),
+    "gdb_eval_depth": (C.c_int, [_P, C.c_int32, C.c_int32, _P] + [C.c_int32] * 4 + [_P, C.c_size_t, _P, C.c_int64, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

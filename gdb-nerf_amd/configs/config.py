@@ -20,7 +20,8 @@ DEFAULTS = {
               "eps": 1.0e-8, "sampler_meta": {"input_views_num": [], "input_views_prob": []}, "optim": "adam", "lr": 5.0e-4,
               "weight_decay": 0.0, "scheduler": {"type": "multi_step", "milestones": [80, 120, 200, 240], "gamma": 0.5}, "batch_size": 4},
     "test": {"batch_size": 1, "collator": "default", "epoch": -1, "batch_sampler": "default",
-             "sampler_meta": {"input_views_num": [], "input_views_prob": []}, "eval_depth": False, "eval_center": False},
+             "sampler_meta": {"input_views_num": [], "input_views_prob": []}, "eval_depth": False, "eval_center": False,
+             "hip_metrics": False},
 }
 
 

@@ -7,7 +7,12 @@ skimage, lpips and cv2 are not in the MI355X image, so the two skimage metrics a
   * structural_similarity(gt, pred, channel_axis=-1) with skimage's defaults for float images:
     7x7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance, data_range 2 (dtype range of
     float images), mean over the interior and the channels                  (reference :86)
-LPIPS needs the `lpips` package and its VGG weights; `eval_lpips: True` without them is an error."""
+LPIPS needs the `lpips` package and its VGG weights; `eval_lpips: True` without them is an error.
+
+`test.hip_metrics: True` (default off) keeps the frame on the device: with fp32 CUDA prediction and ground truth, `evaluate` only
+enqueues the metric kernels of the HIP library (metrics.py, gdb_eval_image / gdb_eval_depth) and returns; each frame leaves a
+row of float64 sums in a device table that `summarize` copies to the host once.  With the switch off, CPU tensors or non-fp32
+images the numpy path below runs unchanged."""
 import math
 import os
 import struct
@@ -15,6 +20,7 @@ import zlib
 from collections import defaultdict
 
 import numpy as np
+import torch
 from scipy.ndimage import uniform_filter
 
 
@@ -65,9 +71,15 @@ def write_png(path: str, rgb_u8: np.ndarray) -> None:
 
 
 class Evaluator:
+    # columns of a frame's row in the device table: the image record, then the depth records of the NeRF and the MVS depth
+    _COLS = 16   # 5 + 4 + 4, padded to whole 128-byte rows
+    _NERF_DEPTH, _MVS_DEPTH = 5, 9
+
     def __init__(self, cfg):
         self.cfg = cfg
         self._reset()
+        self.hip_metrics = bool(getattr(cfg.test, "hip_metrics", False))
+        self._table, self._rows = None, []   # device rows (capacity, _COLS) and per row on the host (scene, SSIM windows, has depth)
         self.loss_fn_vgg = None
         if getattr(cfg, "eval_lpips", False):
             try:
@@ -85,7 +97,91 @@ class Evaluator:
         self.psnrs, self.ssims, self.lpips = [], [], []
         self.scene = defaultdict(lambda: defaultdict(list))
 
+    def use_hip_metrics(self, output, batch) -> bool:
+        """The switch is on, and prediction, ground truth (fp32) and mask are CUDA tensors."""
+        pred, gt, mask = output["rgb"], batch["tar_views"]["rgb"], batch["tar_views"]["mask"]
+        return self.hip_metrics and all(getattr(t, "is_cuda", False) for t in (pred, gt, mask)) and \
+            pred.dtype == gt.dtype == torch.float32
+
+    def _next_rows(self, n, device):
+        """A view of the next n free rows of the device table, which grows by doubling (the copy is enqueued on the stream)."""
+        used = len(self._rows)
+        if self._table is None or self._table.device != device or used + n > self._table.shape[0]:
+            cap = max(64, 2 * (used + n))
+            table = torch.empty((cap, self._COLS), dtype=torch.float64, device=device)
+            if used:
+                table[:used].copy_(self._table[:used])
+            self._table = table
+        return self._table[used:used + n]
+
+    def _evaluate_hip(self, output, batch):
+        """The device path of `evaluate`: enqueue and return.  No host copy, no `.item()`, no synchronising call — except for
+        `save_result`, whose PNG is written from a host copy (that copy waits for the stream), and `eval_lpips`, whose `.item()` does.
+        An image too small for one 7 x 7 window raises ValueError (skimage raises there too; the numpy path returns NaN with a
+        warning)."""
+        from .. import metrics
+        B, _, _, H, W = batch["src_views"]["rgb"].shape
+        pred, gt, mask = output["rgb"].detach(), batch["tar_views"]["rgb"].detach(), batch["tar_views"]["mask"]
+        if mask.dtype != torch.float32:
+            mask = mask.float()   # on the device
+        h, w = gt.shape[1:3]
+        crop = (0, 0, h, w)
+        if self.cfg.test.eval_center:  # the numpy path's [ch:-ch, cw:-cw], with ch, cw from the source views' size as there
+            ch, cw = int(H * 0.1), int(W * 0.1)
+            crop = (ch, cw, max(h - 2 * ch, 0) if ch else 0, max(w - 2 * cw, 0) if cw else 0)
+        rows = self._next_rows(B, gt.device)
+        metrics.eval_image(pred, gt, mask, rows, crop)
+        if getattr(self.cfg, "save_result", False) or self.loss_fn_vgg is not None:
+            pc = pred.permute(0, 2, 3, 1).clamp(0.0, 1.0)[:, crop[0]:crop[0] + crop[2], crop[1]:crop[1] + crop[3]]
+            keep = (mask >= 1)[:, crop[0]:crop[0] + crop[2], crop[1]:crop[1] + crop[3], None]
+        for b in range(B):
+            scene = batch["meta"]["scene"][b]
+            if getattr(self.cfg, "save_result", False):  # a host copy: waits for the stream
+                name = "{}_{}_{}.png".format(scene, batch["meta"]["tar_view"][b].item(), batch["meta"]["frame_id"][b].item())
+                write_png(os.path.join(self.cfg.result_dir, name), (pc[b].cpu().numpy() * 255).clip(0, 255).astype(np.uint8))
+            if self.loss_fn_vgg is not None:
+                t = lambda a: ((a * keep[b])[None].permute(0, 3, 1, 2) - 0.5) * 2.0
+                gc = gt[b, crop[0]:crop[0] + crop[2], crop[1]:crop[1] + crop[3]]
+                v = self.loss_fn_vgg(t(gc), t(pc[b])).item()
+                self.lpips.append(v)
+                self.scene[scene]["lpips"].append(v)
+            depth = bool(self.cfg.test.eval_depth and scene in self.eval_depth_scenes)
+            if depth:
+                row = rows[b:b + 1]
+                metrics.eval_depth(output["nerf_depth"][b:b + 1].detach().float(), batch["tar_views"]["depth"][b:b + 1].float(),
+                                   row[:, self._NERF_DEPTH:], resize=True)
+                metrics.eval_depth(output["mvs_depth"][b:b + 1].detach().float(), batch["tar_gt_ms"]["depth"][-1][b:b + 1].float(),
+                                   row[:, self._MVS_DEPTH:], resize=False)
+            self._rows.append((scene, (crop[2] - 6) * (crop[3] - 6), depth))
+
+    @property
+    def capacity(self) -> int:
+        """Frames the device table holds before it grows again (0 before the first device frame)."""
+        return 0 if self._table is None else int(self._table.shape[0])
+
+    def collect(self):
+        """The frames the device path has enqueued since the last call, onto the host lists: ONE device-to-host copy of their rows,
+        then per frame what the numpy path appends in `evaluate`.  `summarize` calls it."""
+        if not self._rows:
+            return
+        table = self._table[:len(self._rows)].cpu().numpy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for (scene, windows, depth), r in zip(self._rows, table):
+                mse = float(r[0] / (3.0 * r[1]))
+                row = {"psnr": float("inf") if mse == 0 else 10.0 * math.log10(1.0 / mse),
+                       "ssim": float(np.mean(r[2:5] / windows))}
+                for k, v in row.items():
+                    getattr(self, k + "s").append(v)
+                    self.scene[scene][k].append(v)
+                if depth:
+                    for tag, o in (("", self._NERF_DEPTH), ("mvs_", self._MVS_DEPTH)):
+                        for k, i in (("abs", 0), ("acc_2", 1), ("acc_10", 2)):
+                            self.depth[tag + k].append(r[o + i] / r[o + 3])
+        self._rows = []
+
     def evaluate(self, output, batch):
+        if self.use_hip_metrics(output, batch):
+            return self._evaluate_hip(output, batch)
         B, _, _, H, W = batch["src_views"]["rgb"].shape
         gt = batch["tar_views"]["rgb"].detach().cpu().numpy()
         masks = batch["tar_views"]["mask"].cpu().numpy() >= 1
@@ -121,6 +217,7 @@ class Evaluator:
                     self.depth[tag + "acc_10"].append((err < 10).mean())
 
     def summarize(self):
+        self.collect()
         ret = {"psnr": np.mean(self.psnrs), "ssim": np.mean(self.ssims)}
         if self.loss_fn_vgg is not None:
             ret["lpips"] = np.mean(self.lpips)

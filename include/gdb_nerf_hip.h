@@ -491,6 +491,33 @@ int gdb_fpn(int32_t base_channels, int32_t out0, int32_t out1, int32_t out2, con
             const float* d_packed, int32_t level_mask, void* d_workspace, size_t ws_bytes, float* d_level0, float* d_level1,
             float* d_level2, void* stream);
 
+/* ---- the evaluator's metrics (ABI v7, added) -------------------------------------------------------------------------------- */
+/* What evaluators/gdb_nerf.py computes per frame, on the device: every call enqueues its launches on `stream` and leaves one record
+ * of doubles per batch item; nothing is copied to the host and nothing waits.  All arithmetic in fp64 from the fp32 inputs.  Record b
+ * is written at d_records + b * record_stride (record_stride in doubles, at least the record's length), so records can go straight
+ * into the rows of a larger table.  Deterministic: per-workgroup partial sums in d_workspace, added in a fixed order by a second
+ * launch, no atomics; the workspace's and the records' previous contents do not matter.
+ * gdb_eval_workspace_bytes: enough for either call on B images or ground-truth depth maps of H x W.
+ * gdb_eval_image: d_pred (B, 3, H, W) as Network.forward returns it (clamped to [0, 1] here), d_gt (B, H, W, 3), d_mask (B, H, W) with
+ * the rule mask >= 1, all read in place; the crop is rows [crop_y0, crop_y0 + crop_h), columns [crop_x0, crop_x0 + crop_w) of the
+ * image (0, 0, H, W for all of it).  Record (GDB_EVAL_IMAGE_REC doubles): [sum of (gt - pred)^2 over the masked pixels' three
+ * channels, masked pixels, then per channel the sum of the SSIM map over the (crop_h - 6) x (crop_w - 6) windows that lie inside the
+ * crop, of the images zeroed outside the mask]; SSIM per window: 7 x 7 means, sample covariance (x 49 / 48), K1 0.01, K2 0.03, data
+ * range 2.  GDB_E_SHAPE for B, H or W < 1, a crop outside the image or one with fewer than 7 rows or columns.
+ * gdb_eval_depth: d_depth (B, Hd, Wd) against d_gt (B, H, W) over the pixels with gt != 0; resize != 0 resamples d_depth to H x W
+ * (bilinear, half-pixel centres, edge clamp, i.e. cv2.INTER_LINEAR), resize == 0 needs Hd == H and Wd == W (GDB_E_SHAPE otherwise).
+ * Record (GDB_EVAL_DEPTH_REC doubles): [sum of |err|, count(|err| < 2), count(|err| < 10), count(gt != 0)].
+ * GDB_E_BADARG for a NULL pointer or a short record_stride, GDB_E_WORKSPACE for a short workspace; every refusal comes before the
+ * first launch. */
+#define GDB_EVAL_IMAGE_REC 5
+#define GDB_EVAL_DEPTH_REC 4
+int gdb_eval_workspace_bytes(int32_t B, int32_t H, int32_t W, size_t* out_bytes);
+int gdb_eval_image(const float* d_pred, const float* d_gt, const float* d_mask, int32_t B, int32_t H, int32_t W, int32_t crop_y0,
+                   int32_t crop_x0, int32_t crop_h, int32_t crop_w, void* d_workspace, size_t ws_bytes, double* d_records,
+                   int64_t record_stride, void* stream);
+int gdb_eval_depth(const float* d_depth, int32_t Hd, int32_t Wd, const float* d_gt, int32_t B, int32_t H, int32_t W, int32_t resize,
+                   void* d_workspace, size_t ws_bytes, double* d_records, int64_t record_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
