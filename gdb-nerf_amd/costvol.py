@@ -43,9 +43,9 @@ def build_feature_volume(src_feat, src_exts, src_ints, tar_exts, tar_ints, depth
 def depth_regression(depth_values, depth_prob, ci_scale: float, inv_depth: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     lib = _lib.load()
     B, D, H, W = depth_values.shape
-    dv, pr = _c(depth_values, "depth_values"), _c(depth_prob, "depth_prob")
-    if tuple(pr.shape) != (B, D, H, W):
+    if tuple(depth_prob.shape) != (B, D, H, W):
         raise ValueError("depth_prob shape differs from depth_values")
+    dv, pr = _c(depth_values, "depth_values"), _c(depth_prob, "depth_prob")
     depth = torch.empty((B, 1, H, W), device=dv.device)
     ci = torch.empty((B, 2, H, W), device=dv.device)
     _lib.check(lib.gdb_depth_regression(dv.data_ptr(), pr.data_ptr(), B, D, H, W, C.c_float(float(ci_scale)), int(bool(inv_depth)),

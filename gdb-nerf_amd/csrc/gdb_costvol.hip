@@ -209,18 +209,23 @@ static int build_feature_volume(const float* d_src_feat, const float* d_src_exts
     if (B < 1 || V < 1 || C < 1 || Hs < 1 || Ws < 2 || D < 1 || Ht < 1 || Wt < 1) return gdb_fail(GDB_E_SHAPE, "bad cost-volume shape");
     if (V > GDB_MAX_VIEWS) return gdb_fail(GDB_E_SHAPE, "V=%d exceeds %d views", V, GDB_MAX_VIEWS);
     if ((size_t)C * Hs * Ws >= ((size_t)1 << 32)) return gdb_fail(GDB_E_SHAPE, "source feature map too large for 32-bit offsets");
-    hipStream_t st = (hipStream_t)stream_;
-    hipLaunchKernelGGL(k_costvol_proj, dim3((B * V + 63) / 64), dim3(64), 0, st, B, V, d_src_exts, d_src_ints, d_tar_exts, d_tar_ints, d_proj_ws);
-    LAUNCH_CHECK("k_costvol_proj");
     // channels per thread: all of them (splitting channels over more threads measured no faster on MI355X:
     // 44 / 118 us at the two DTU stage shapes for cpt = 32, 8, 4); GDB_COSTVOL_CPT overrides in the diagnostic build
     int cpt = C;
 #ifdef GDB_DIAG  // diagnostic build only: the product entry reads no environment
     if (getenv("GDB_COSTVOL_CPT")) cpt = atoi(getenv("GDB_COSTVOL_CPT")) > 0 ? atoi(getenv("GDB_COSTVOL_CPT")) : C;
 #endif
-    const int tiles = (Ht * Wt + 255) / 256, groups = (C + cpt - 1) / cpt;
-    if ((size_t)B * tiles * D * groups >= ((size_t)1 << 31)) return gdb_fail(GDB_E_SHAPE, "cost volume too large for the launch grid");
-    const int nblk = B * tiles * D * groups;
+    // every refusal comes before the first launch; the plane and the block count in 64 bits (Ht * Wt may not fit an int, and the grid
+    // is the block count rounded up to a multiple of 8)
+    const size_t plane_t = (size_t)Ht * Wt, tiles_ = (plane_t + 255) / 256;
+    const int groups = (C + cpt - 1) / cpt;
+    const size_t lim = ((size_t)1 << 31) - 8;   // each partial product stays below 2^62
+    if (plane_t >= lim || (size_t)B * tiles_ >= lim || (size_t)B * tiles_ * D >= lim || (size_t)B * tiles_ * D * groups >= lim)
+        return gdb_fail(GDB_E_SHAPE, "cost volume too large for the launch grid");
+    const int tiles = (int)tiles_, nblk = B * tiles * D * groups;
+    hipStream_t st = (hipStream_t)stream_;
+    hipLaunchKernelGGL(k_costvol_proj, dim3((B * V + 63) / 64), dim3(64), 0, st, B, V, d_src_exts, d_src_ints, d_tar_exts, d_tar_ints, d_proj_ws);
+    LAUNCH_CHECK("k_costvol_proj");
     // The channel-pair form: given C * Hs * Ws * V * B floats of scratch (gdb_build_feature_volume_ws) and an even channel count, the
     // source maps are re-laid once ([c / 2][y][x][2], k_costvol_pairs) and the sweep loads 16 bytes per (channel PAIR, row, view)
     // instead of 8 per (channel, row, view): half the load instructions of a kernel the texture addresser bounds.  Bit-identical.
