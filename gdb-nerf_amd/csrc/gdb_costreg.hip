@@ -370,6 +370,11 @@ static int cr_launch(const CrArgs& a, hipStream_t st) {
 // the launch geometry of layer li; GDB_E_SHAPE when the grid would overflow
 static int cr_args(const CrPlan& P, int li, int B, int D, int H, int W, CrArgs* pa) {
     const CrLayer& l = P.L[li];
+    // After conv0 every stride-1 and every transposed BN layer reads c << (level + 1) channels, a multiple of 16, into at least 16
+    // rows: E = 4 at one plane per wave is the only form cr_plan asks for, and the only one built (cr_layer).
+    if (li > 0 && li < P.nlayers - 1 && l.mode != CR_S2 && (l.e != 4 || l.zs != 1))
+        return gdb_fail(GDB_E_BADARG, "cost reg: layer %d (mode %d, %d -> %d channels) asks for a kernel that is not built (E = %d, %d planes per wave)",
+                        li, l.mode, l.cin, l.cout, l.e, l.zs);
     CrArgs& a = *pa;
     a = CrArgs{};
     a.B = B; a.cin = l.cin; a.cout = l.cout;
@@ -390,13 +395,9 @@ static int cr_layer(const CrPlan& P, int li, const CrArgs& a, hipStream_t st) {
     const CrLayer& l = P.L[li];
     if (li == P.nlayers - 1) return l.e == 4 ? cr_launch<CR_S1, 4, false, 1, CR_HEADS>(a, st) : cr_launch<CR_S1, 2, false, 1, CR_HEADS>(a, st);
     if (l.nc) return l.zs == 2 ? cr_launch<CR_S1, 4, true, 2, CR_BN>(a, st) : cr_launch<CR_S1, 4, true, 1, CR_BN>(a, st);
-    switch (l.mode) {
-        case CR_S1:
-            if (l.zs == 2) return l.e == 4 ? cr_launch<CR_S1, 4, false, 2, CR_BN>(a, st) : cr_launch<CR_S1, 2, false, 2, CR_BN>(a, st);
-            return l.e == 4 ? cr_launch<CR_S1, 4, false, 1, CR_BN>(a, st) : cr_launch<CR_S1, 2, false, 1, CR_BN>(a, st);
-        case CR_S2: return l.e == 4 ? cr_launch<CR_S2, 4, false, 1, CR_BN>(a, st) : cr_launch<CR_S2, 2, false, 1, CR_BN>(a, st);
-        default: return l.e == 4 ? cr_launch<CR_UP, 4, false, 1, CR_BN>(a, st) : cr_launch<CR_UP, 2, false, 1, CR_BN>(a, st);
-    }
+    // After conv0 only the stride-2 layers meet 8-channel chunks (cr_args has refused everything else that is not built).
+    if (l.mode == CR_S2) return l.e == 4 ? cr_launch<CR_S2, 4, false, 1, CR_BN>(a, st) : cr_launch<CR_S2, 2, false, 1, CR_BN>(a, st);
+    return l.mode == CR_S1 ? cr_launch<CR_S1, 4, false, 1, CR_BN>(a, st) : cr_launch<CR_UP, 4, false, 1, CR_BN>(a, st);
 }
 
 extern "C" int gdb_cost_reg(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B, int32_t D,

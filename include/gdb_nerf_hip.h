@@ -450,7 +450,14 @@ int gdb_decode_rows(const GdbConfig* cfg, const GdbFrame* shape, const float* d_
  * gdb_cost_reg_workspace_bytes / gdb_cost_reg: d_cost (B, cin, D, H, W) as gdb_build_feature_volume writes it, read in place; D, H
  * and W divisible by 2^depth (GDB_E_SHAPE otherwise), ws_bytes >= the workspace size (GDB_E_WORKSPACE otherwise; its contents do
  * not matter).  Out: d_volume (B, cout, D, H, W), d_prob (B, D, H, W) = softmax over D of prob_head.  Every refusal comes before
- * the first launch.  Deterministic (no atomics). */
+ * the first launch.  Deterministic (no atomics).
+ * The workspace is the caller's, and after the call it still holds every intermediate, channel-last, in this order:
+ *   S_0 | S_1 T_1 | ... | S_depth T_depth,   S_l and T_l: (B, D >> l, H >> l, W >> l, base << l) floats, each rounded up to a
+ *   multiple of 64 floats (the padding is never written); the byte count is 4 x the sum (no T_0).
+ * T_l (l >= 1) is the output of the stride-2 conv(2l - 1).  S_depth is the output of the deepest stride-1 layer, conv(2 depth).
+ * S_l for l < depth was the skip (conv0, or conv(2l)) and is left in its final state, skip + the transposed convolution that
+ * writes level l (conv(3 depth - l)): the value the next layer up, or for l = 0 the two heads, read.  The skips themselves are
+ * overwritten by that add. */
 int gdb_cost_reg_packed_floats(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, size_t* out_floats);
 int gdb_pack_cost_reg_weights(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* const* h_tensors, float* h_out);
 int gdb_cost_reg_workspace_bytes(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, int32_t B, int32_t D, int32_t H,
