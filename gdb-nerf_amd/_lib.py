@@ -90,6 +90,10 @@ _SIGNATURES = {
     "gdb_pack_cost_reg_weights": (C.c_int, [C.c_int32] * 4 + [C.POINTER(_P), _P]),
     "gdb_cost_reg_workspace_bytes": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_size_t)]),
     "gdb_cost_reg": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 4 + [_P, _P, C.c_size_t, _P, _P, _P]),
+    "gdb_mvs_stage_workspace_bytes": (C.c_int, [C.c_int32] * 12 + [C.POINTER(C.c_size_t)]),
+    "gdb_mvs_stage": (C.c_int, [_P] * 5 + [C.c_float, C.c_float, _P, C.c_int32, C.c_int32, C.c_double] + [C.c_int32] * 9 + [C.c_float]
+                      + [C.c_int32] * 4 + [_P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
+    "gdb_mvs_hypotheses": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double] + [C.c_int32] * 5 + [_P, _P]),
     "gdb_fpn_packed_floats": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_size_t)]),
     "gdb_pack_fpn_weights": (C.c_int, [C.c_int32] * 4 + [C.POINTER(_P), _P]),
     "gdb_fpn_workspace_bytes": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_size_t)]),

@@ -1,7 +1,7 @@
 """Torch-facing wrappers of the two "next"-row kernels: the plane-sweep cost volume
 and the depth regression of the cascade MVS stage, same signatures as the reference functions
 (networks/gdb_nerf/depth_net.py:424-514), and `CostReg`, the HIP forward of the cascade's cost-regularisation 3-D U-Nets
-(networks/gdb_nerf/cost_reg_net.py).  CUDA tensors only — there is no CPU fallback here either."""
+(networks/gdb_nerf/cost_reg_net.py), and `MvsStage`, one whole cascade stage as one library call.  CUDA tensors only — there is no CPU fallback here either."""
 import ctypes as C
 from typing import Tuple
 
@@ -117,3 +117,71 @@ class CostReg:
         _lib.check(lib.gdb_cost_reg(self.depth, self.cin, self.c, self.cout, cost.data_ptr(), B, D, H, W, packed.data_ptr(), ws.data_ptr(),
                                     nbytes.value, volume.data_ptr(), prob.data_ptr(), torch.cuda.current_stream(cost.device).cuda_stream))
         return volume, prob
+
+
+def _range_dims(search: torch.Tensor):
+    if search.dim() == 2:   # (B, 2) near / far: broadcast over the target
+        return 1, 1
+    if search.dim() != 4 or search.shape[1] != 2:
+        raise ValueError(f"search range of shape {tuple(search.shape)}, expected (B, 2) or (B, 2, hr, wr)")
+    return int(search.shape[2]), int(search.shape[3])
+
+
+def mvs_hypotheses(search: torch.Tensor, ratio: float, num_depth: int, Ht: int, Wt: int, inv_depth: bool) -> torch.Tensor:
+    """The (B, num_depth, Ht, Wt) hypotheses a stage computes in its kernels from `search` ((B, 2) or (B, 2, 1, 1): broadcast;
+    (B, 2, hr, wr): upsampled by `ratio` as F.interpolate(scale_factor=ratio, mode="bilinear", align_corners=False) does), then
+    `get_depth_values`.  For tests and diagnosis: MvsStage never materialises them."""
+    lib = _lib.load()
+    search = _c(search, "search")
+    hr, wr = _range_dims(search)
+    out = torch.empty((search.shape[0], num_depth, Ht, Wt), device=search.device)
+    _lib.check(lib.gdb_mvs_hypotheses(search.data_ptr(), hr, wr, float(ratio), search.shape[0], num_depth, Ht, Wt, int(bool(inv_depth)),
+                                      out.data_ptr(), torch.cuda.current_stream(search.device).cuda_stream))
+    return out
+
+
+class MvsStage:
+    """One cascade stage of `DepthNet.forward` on the HIP library (gdb_mvs_stage): camera set-up from the unscaled intrinsics, the
+    plane sweep with its hypotheses computed in the kernel from `search`, the stage's U-Net, softmax over D and depth regression.
+    `MvsStage(reg)` shares the weight pack of the `CostReg` it is given.  Returns (volume (B, out, D, Ht, Wt), depth (B, Ht, Wt),
+    ci (B, 2, Ht, Wt), vol_range (B, 2, Ht, Wt)) on the current stream; no tensor op and, once the weights are packed, no host
+    synchronisation."""
+
+    def __init__(self, reg: CostReg) -> None:
+        self.reg = reg
+
+    def workspace_bytes(self, B, V, Cc, Hs, Ws, D, Ht, Wt) -> int:
+        r, n = self.reg, C.c_size_t()
+        _lib.check(_lib.load().gdb_mvs_stage_workspace_bytes(B, V, Cc, Hs, Ws, D, Ht, Wt, r.depth, r.cin, r.c, r.cout, C.byref(n)))
+        return n.value
+
+    def __call__(self, src_feat, src_exts, src_ints, tar_exts, tar_ints, feat_scale: float, vol_scale: float, search, ratio: float,
+                 num_depth: int, Ht: int, Wt: int, inv_depth: bool, ci_scale: float, workspace: torch.Tensor = None):
+        lib, r = _lib.load(), self.reg
+        if src_feat.dim() != 5:
+            raise ValueError(f"src_feat of shape {tuple(src_feat.shape)}, expected (B, V, C, Hs, Ws)")
+        B, V, Cc, Hs, Ws = src_feat.shape
+        if tuple(src_exts.shape) != (B, V, 4, 4) or tuple(src_ints.shape) != (B, V, 3, 3) or tuple(tar_exts.shape) != (B, 4, 4) \
+                or tuple(tar_ints.shape) != (B, 3, 3) or search.shape[0] != B:
+            raise ValueError("inconsistent cost-volume shapes")
+        args = [_c(t, n) for t, n in ((src_feat, "src_feat"), (src_exts, "src_exts"), (src_ints, "src_ints"), (tar_exts, "tar_exts"),
+                                      (tar_ints, "tar_ints"))]
+        search = _c(search, "search")
+        hr, wr = _range_dims(search)
+        dev = src_feat.device
+        packed = r.pack(dev)
+        nbytes = self.workspace_bytes(B, V, Cc, Hs, Ws, num_depth, Ht, Wt)
+        if workspace is None:   # per call from torch's caching allocator, as CostReg does
+            workspace = torch.empty(((nbytes + 3) // 4,), device=dev)
+        elif not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < nbytes:
+            raise ValueError(f"workspace must be a contiguous CUDA tensor of at least {nbytes} bytes")
+        volume = torch.empty((B, r.cout, num_depth, Ht, Wt), device=dev)
+        depth = torch.empty((B, Ht, Wt), device=dev)
+        ci = torch.empty((B, 2, Ht, Wt), device=dev)
+        vol_range = torch.empty((B, 2, Ht, Wt), device=dev)
+        _lib.check(lib.gdb_mvs_stage(*(t.data_ptr() for t in args), C.c_float(float(feat_scale)), C.c_float(float(vol_scale)),
+                                     search.data_ptr(), hr, wr, float(ratio), B, V, Cc, Hs, Ws, num_depth, Ht, Wt, int(bool(inv_depth)),
+                                     C.c_float(float(ci_scale)), r.depth, r.cin, r.c, r.cout, packed.data_ptr(), workspace.data_ptr(),
+                                     workspace.numel() * workspace.element_size(), volume.data_ptr(), depth.data_ptr(), ci.data_ptr(),
+                                     vol_range.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return volume, depth, ci, vol_range

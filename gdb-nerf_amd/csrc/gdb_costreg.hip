@@ -400,9 +400,11 @@ static int cr_layer(const CrPlan& P, int li, const CrArgs& a, hipStream_t st) {
     return l.mode == CR_S1 ? cr_launch<CR_S1, 4, false, 1, CR_BN>(a, st) : cr_launch<CR_UP, 4, false, 1, CR_BN>(a, st);
 }
 
-extern "C" int gdb_cost_reg(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B, int32_t D,
-                            int32_t H, int32_t W, const float* d_packed, void* d_ws, size_t ws_bytes, float* d_volume, float* d_prob,
-                            void* stream_) {
+// mode 1: the whole U-Net with the softmax over D (gdb_cost_reg).  mode 0: up to the prob head's logits, left in d_prob, for the
+// cascade stage's fused softmax and depth regression (gdb_cascade.hip).  mode 2: the refusals alone, nothing is launched.
+int gdb_cost_reg_run_(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B, int32_t D,
+                      int32_t H, int32_t W, const float* d_packed, void* d_ws, size_t ws_bytes, float* d_volume, float* d_prob,
+                      int mode, void* stream_) {
     CrPlan P;
     int rc = cr_plan(depth, cin, base_channels, cout, &P);
     if (rc != GDB_OK) return rc;
@@ -414,6 +416,7 @@ extern "C" int gdb_cost_reg(int32_t depth, int32_t cin, int32_t base_channels, i
     CrArgs A[CR_MAX_LAYERS];
     for (int li = 0; li < P.nlayers; ++li)
         if ((rc = cr_args(P, li, B, D, H, W, &A[li])) != GDB_OK) return rc;
+    if (mode == 2) return GDB_OK;
     float* S[4] = {};
     float* T[4] = {};
     float* p = (float*)d_ws;
@@ -438,8 +441,15 @@ extern "C" int gdb_cost_reg(int32_t depth, int32_t cin, int32_t base_channels, i
     hipStream_t st = (hipStream_t)stream_;
     for (int i = 0; i < P.nlayers; ++i)
         if ((rc = cr_layer(P, i, A[i], st)) != GDB_OK) return rc;
+    if (mode == 0) return GDB_OK;
     const size_t HW = (size_t)H * W, n = (size_t)B * HW;
     hipLaunchKernelGGL(k_costreg_softmax, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_prob, B, D, HW);
     LAUNCH_CHECK("k_costreg_softmax");
     return GDB_OK;
+}
+
+extern "C" int gdb_cost_reg(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B, int32_t D,
+                            int32_t H, int32_t W, const float* d_packed, void* d_ws, size_t ws_bytes, float* d_volume, float* d_prob,
+                            void* stream_) {
+    return gdb_cost_reg_run_(depth, cin, base_channels, cout, d_cost, B, D, H, W, d_packed, d_ws, ws_bytes, d_volume, d_prob, 1, stream_);
 }

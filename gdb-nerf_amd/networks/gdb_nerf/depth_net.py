@@ -99,6 +99,8 @@ class DepthNet(nn.Module):
         # the 3-D U-Nets on the HIP library (costvol.CostReg): eval mode and fp32 CUDA input only; off by default
         self.hip_cost_reg = bool(getattr(mvs, "hip_cost_reg", False))
         self._hip_regs = {}   # stage -> costvol.CostReg (not a module: no state-dict keys)
+        # a whole stage as one library call (costvol.MvsStage): eval mode and fp32 CUDA inputs only; off by default
+        self.hip_cascade = bool(getattr(mvs, "hip_cascade", False))
         # the reference indexes feat_dims by the pyramid level again (depth_net.py:32-37); kept for key/shape parity
         nets = [CostRegNet_small(self.feat_dims[self.vol_levels[0]], mvs.voxel_dim, fpn.base_channels)]
         nets += [CostRegNet(self.feat_dims[self.vol_levels[i]], mvs.voxel_dim, fpn.base_channels) for i in range(1, self.num_stages)]
@@ -110,14 +112,38 @@ class DepthNet(nn.Module):
         """The HIP U-Net needs the switch, eval mode (training needs batch statistics and autograd) and fp32 CUDA tensors."""
         return self.hip_cost_reg and not self.training and _use_hip(feats, True)
 
-    def _cost_reg(self, s: int, cost: torch.Tensor, feats: torch.Tensor):
-        if not self.use_hip_cost_reg(feats):
-            return self.cost_regs[s](cost)
+    def use_hip_cascade(self, *tensors) -> bool:
+        """One MvsStage call per stage needs the switch, eval mode and fp32 CUDA tensors throughout."""
+        return self.hip_cascade and not self.training and all(_use_hip(t, True) for t in tensors)
+
+    def _hip_reg(self, s: int):
         from ... import costvol
         reg = self._hip_regs.get(s)
         if reg is None or reg.module is not self.cost_regs[s]:
             reg = self._hip_regs[s] = costvol.CostReg(self.cost_regs[s])
-        return reg(cost)
+        return reg
+
+    def _cost_reg(self, s: int, cost: torch.Tensor, feats: torch.Tensor):
+        if not self.use_hip_cost_reg(feats):
+            return self.cost_regs[s](cost)
+        return self._hip_reg(s)(cost)
+
+    def _forward_hip_cascade(self, H0: int, W0: int, ms_feats, src_exts, src_ints, tar_exts, tar_ints, near_far):
+        from ... import costvol
+        depths, ranges, vol_ranges, volumes = [], [], [], []
+        search, ratio = near_far, 1.0   # (B,2): broadcast by the library
+        for s in range(self.num_stages):
+            Hs, Ws = int(H0 * self.vol_scales[s]), int(W0 * self.vol_scales[s])
+            volume, depth, search, vol_range = costvol.MvsStage(self._hip_reg(s))(
+                ms_feats[self.vol_levels[s]], src_exts, src_ints, tar_exts, tar_ints, self.feat_scales[s], self.vol_scales[s], search, ratio,
+                self.num_depth[s], Hs, Ws, self.inv_depth[s], self.ci_scales[s])
+            depths.append(depth)
+            ranges.append(search)
+            vol_ranges.append(vol_range)
+            volumes.append(volume)
+            if s < self.num_stages - 1:   # the next stage upsamples this interval in its kernels
+                ratio = self.vol_scales[s + 1] / self.vol_scales[s]
+        return depths, ranges, vol_ranges, volumes, []
 
     def _load_from_state_dict(self, *args, **kwargs):
         for reg in self._hip_regs.values():
@@ -128,6 +154,8 @@ class DepthNet(nn.Module):
         """Returns (depths, depth_ranges, vol_ranges, feat_volumes, rgb_predictions) per stage like the
         reference; rgb_predictions (train-time supervision) is always empty here."""
         B, V, _, H0, W0 = src_images.shape
+        if self.use_hip_cascade(src_images, *(ms_feats[l] for l in self.vol_levels), src_exts, src_ints, tar_exts, tar_ints, near_far):
+            return self._forward_hip_cascade(H0, W0, ms_feats, src_exts, src_ints, tar_exts, tar_ints, near_far)
         depths, ranges, vol_ranges, volumes = [], [], [], []
         search = near_far[..., None, None]  # (B,2,1,1)
         for s in range(self.num_stages):

@@ -525,6 +525,37 @@ int gdb_eval_image(const float* d_pred, const float* d_gt, const float* d_mask, 
 int gdb_eval_depth(const float* d_depth, int32_t Hd, int32_t Wd, const float* d_gt, int32_t B, int32_t H, int32_t W, int32_t resize,
                    void* d_workspace, size_t ws_bytes, double* d_records, int64_t record_stride, void* stream);
 
+/* ---- one cascade MVS stage as one call (ABI v7, added) ------------------------------------------------------------------------
+ * One stage of DepthNet.forward (networks/gdb_nerf/depth_net.py:133-156): camera set-up, plane sweep, the stage's U-Net, softmax
+ * over D and depth regression.  Nothing syncs with the host; deterministic (no atomics); the caller owns all memory.
+ *
+ * Search range d_range (B, 2, hr, wr), channel 0 = lo, 1 = hi (depths).  hr = wr = 1: broadcast over the target (stage 0's
+ * near / far; `ratio` is ignored).  Otherwise the previous stage's interval: pixel (y, x) of the (Ht, Wt) target takes the bilinear
+ * sample F.interpolate(scale_factor = ratio, mode = "bilinear", align_corners = False) takes, src = max((dst + 0.5) / ratio - 0.5, 0),
+ * neighbours clamped to the last row / column (a target larger than ratio x (hr, wr) repeats the last sample).  The hypothesis of
+ * plane d is lo' + (hi' - lo') * step_d, lo' / hi' the sampled ends or, with inv_depth, their reciprocals, step_d =
+ * torch.linspace(0, 1, D)[d] in fp32; every multiply-add rounds twice, as the separate torch ops do.
+ *
+ * gdb_mvs_hypotheses writes these (B, D, Ht, Wt) hypotheses to d_out: a test and diagnosis entry, the stage never materialises them.
+ *
+ * gdb_mvs_stage: d_src_feat (B, V, C, Hs, Ws); d_src_exts (B, V, 4, 4), d_src_ints (B, V, 3, 3), d_tar_exts (B, 4, 4), d_tar_ints
+ * (B, 3, 3) with the UNSCALED intrinsics: rows 0-1 are multiplied by feat_scale (source) / vol_scale (target) in fp32 before the
+ * projection products, as `K[..., :2, :] *= s` does.  The U-Net is (depth, cin = C, base_channels, cout) with d_packed in
+ * gdb_pack_cost_reg_weights' format; D, Ht and Wt divisible by 2^depth, D <= 512.  Out: d_volume (B, cout, D, Ht, Wt) the feat
+ * head's output, d_depth (B, Ht, Wt), d_ci (B, 2, Ht, Wt) = mean -/+ ci_scale * std clipped to the hypothesis range (depths), and
+ * d_vol_range (B, 2, Ht, Wt) = the first and last hypothesis (disparities under inv_depth, as depth_net.py:153 returns them).  The
+ * softmax probabilities are never written.  ws_bytes >= gdb_mvs_stage_workspace_bytes (GDB_E_WORKSPACE otherwise); the workspace's
+ * contents do not matter.  Every refusal comes before the first launch. */
+int gdb_mvs_stage_workspace_bytes(int32_t B, int32_t V, int32_t C, int32_t Hs, int32_t Ws, int32_t D, int32_t Ht, int32_t Wt,
+                                  int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, size_t* out_bytes);
+int gdb_mvs_stage(const float* d_src_feat, const float* d_src_exts, const float* d_src_ints, const float* d_tar_exts,
+                  const float* d_tar_ints, float feat_scale, float vol_scale, const float* d_range, int32_t hr, int32_t wr, double ratio,
+                  int32_t B, int32_t V, int32_t C, int32_t Hs, int32_t Ws, int32_t D, int32_t Ht, int32_t Wt, int32_t inv_depth,
+                  float ci_scale, int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_packed,
+                  void* d_workspace, size_t ws_bytes, float* d_volume, float* d_depth, float* d_ci, float* d_vol_range, void* stream);
+int gdb_mvs_hypotheses(const float* d_range, int32_t hr, int32_t wr, double ratio, int32_t B, int32_t D, int32_t Ht, int32_t Wt,
+                       int32_t inv_depth, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
