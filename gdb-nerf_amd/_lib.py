@@ -22,6 +22,7 @@ PREP_PYR16_ONLY = 2
 PREP_SOURCES_READY = 4
 PREP_STRIP_REACH = 8
 PREP_STRIP_WHOLE = 16
+DECF16_KEEP_LAYERS = 1   # gdb_decode_f16: every layer output, gate and trunk in a workspace region of its own
 
 GDB_OK, GDB_E_BADARG, GDB_E_SHAPE, GDB_E_HIP, GDB_E_WORKSPACE = 0, -1, -2, -3, -4
 GDB_MAX_SAMPLES, GDB_MAX_MIP, GDB_MAX_VIEWS = 16, 3, 8
@@ -39,6 +40,12 @@ class GdbFrame(C.Structure):
                [(n, C.c_void_p) for n in (
                    "d_src_images", "d_img_feat", "d_feat_volume", "d_depth_range", "d_vol_range",
                    "d_src_exts", "d_src_ints", "d_tar_exts", "d_tar_ints", "d_near_far")]
+
+
+class GdbDecF16Region(C.Structure):
+    """A named activation region of the f16 decoder's workspace (gdb_decoder_f16_layout)."""
+    _fields_ = [("name", C.c_char * 32), ("offset", C.c_uint64), ("channels", C.c_int32), ("dtype", C.c_int32),
+                ("per_pixel", C.c_int32), ("reserved", C.c_int32)]
 
 
 class GdbError(RuntimeError):
@@ -80,6 +87,11 @@ _SIGNATURES = {
     "gdb_pack_decoder_weights": (C.c_int, [_CFG, C.c_int32, C.POINTER(_P), _P]),
     "gdb_decoder_workspace_bytes": (C.c_int, [_CFG, _FRM, C.POINTER(C.c_size_t)]),
     "gdb_decode": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
+    "gdb_decoder_f16_packed_bytes": (C.c_int, [_CFG, C.c_int32, C.POINTER(C.c_size_t)]),
+    "gdb_pack_decoder_weights_f16": (C.c_int, [_CFG, C.c_int32, C.POINTER(_P), _P]),
+    "gdb_decoder_f16_workspace_bytes": (C.c_int, [_CFG, _FRM, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "gdb_decoder_f16_layout": (C.c_int, [_CFG, _FRM, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "gdb_decode_f16": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
     "gdb_decoder_rows_workspace_bytes": (C.c_int, [_CFG, _FRM, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "gdb_decoder_rows_layout": (C.c_int, [_CFG, _FRM, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -716,6 +716,15 @@ __global__ void __launch_bounds__(256) k_se_gate(const float* __restrict__ part,
     if (threadIdx.x == 0) count[b] = 0u;
 }
 
+// k_se_gate for the f16 decoder (gdb_decoder_f16.hip keeps `part` in the layout above): the group count of nseg segments, and the launch.
+int gdb_dec_se_groups(int nseg) { return (nseg + DEC_SEG - 1) / DEC_SEG; }
+hipError_t gdb_dec_se_gate_launch(const float* part, int B, int nseg, float inv_hw, const float* w1, const float* w2, float* part2,
+                                  unsigned* count, float* gate, hipStream_t st) {
+    const int ngrp = gdb_dec_se_groups(nseg);
+    hipLaunchKernelGGL(k_se_gate, dim3((unsigned)(B * ngrp)), dim3(256), 0, st, part, nseg, ngrp, inv_hw, w1, w2, part2, count, gate);
+    return hipGetLastError();
+}
+
 // upscale_factor 4: the dense blocks' output with the last squeeze-excitation gate and the global residual applied,
 // x = P + T * gate + S (decoder_rdn.py:40, :78), as its own (tiny: the b = 4 bundle map is a sixteenth of the image) element-wise pass -
 // the four sub-pixel convolutions of the first up stage all read it.  Rounded as the fused apply of the bundle_size 2 path rounds.

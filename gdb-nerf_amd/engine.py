@@ -405,6 +405,64 @@ class HotPathEngine:
         host = np.zeros(n.value, dtype=np.float32)
         _lib.check(self.lib.gdb_pack_decoder_weights(C.byref(self.cfg), int(num_layers), ptrs, host.ctypes.data))
         self.dec_weights, self.dec_layers = torch.from_numpy(host).to(self.device), int(num_layers)
+        self._dec_state_f16, self.dec_weights_f16 = (ptrs, arrs), None   # the f16 form is packed at the first decode_f16()
+
+    def _pack_decoder_f16(self) -> torch.Tensor:
+        """The f16 decoder's packed buffer (gdb_pack_decoder_weights_f16) from the tensors of the last load_decoder_weights()."""
+        if getattr(self, "dec_weights_f16", None) is None:
+            if getattr(self, "_dec_state_f16", None) is None:
+                raise ValueError("load_decoder_weights() first")
+            ptrs, _arrs = self._dec_state_f16
+            n = C.c_size_t()
+            _lib.check(self.lib.gdb_decoder_f16_packed_bytes(C.byref(self.cfg), self.dec_layers, C.byref(n)))
+            host = np.zeros(n.value, dtype=np.uint8)
+            _lib.check(self.lib.gdb_pack_decoder_weights_f16(C.byref(self.cfg), self.dec_layers, ptrs, host.ctypes.data))
+            self.dec_weights_f16 = torch.from_numpy(host).to(self.device)
+        return self.dec_weights_f16
+
+    @_on_device
+    def decode_f16(self, bundle_feat: torch.Tensor, keep_layers: bool = False) -> torch.Tensor:
+        """The decoder on plain f16 MFMA with half-precision activations (gdb_decode_f16; bundle_size 2): the same arguments and result
+        as `decode`, under the narrower contract of DESIGN.md section 4.10.  keep_layers: every layer's output, every gate and every
+        trunk stays in a workspace region of its own for `decoder_f16_activations()`; rgb_c is bit-identical either way."""
+        packed_w = self._pack_decoder_f16()
+        f = self._need_frame()
+        nb = self.n_bundles
+        if bundle_feat.dim() != 2 or bundle_feat.shape[0] != nb or bundle_feat.shape[1] < self.Q:
+            raise ValueError(f"bundle_feat has shape {tuple(bundle_feat.shape)}, expected ({nb}, >= {self.Q})")
+        _chk(bundle_feat, "bundle_feat")
+        flags = _lib.DECF16_KEEP_LAYERS if keep_layers else 0
+        need = C.c_size_t()
+        _lib.check(self.lib.gdb_decoder_f16_workspace_bytes(C.byref(self.cfg), C.byref(f), self.dec_layers, flags, C.byref(need)))
+        if getattr(self, "_dec_ws_f16", None) is None or self._dec_ws_f16.numel() < need.value:
+            self._dec_ws_f16 = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        rgb_c = self._buf("decode.rgb_c", (f.B, 3, f.H * 2, f.W * 2), internal=True)
+        _lib.check(self.lib.gdb_decode_f16(C.byref(self.cfg), C.byref(f), bundle_feat.data_ptr(), int(bundle_feat.shape[1]), packed_w.data_ptr(),
+                                           self.dec_layers, flags, self._dec_ws_f16.data_ptr(), self._dec_ws_f16.numel(), rgb_c.data_ptr(),
+                                           self._stream()))
+        self._dec_f16_kept = (f.B, f.H, f.W, self.dec_layers) if keep_layers else None
+        return rgb_c
+
+    def decoder_f16_activations(self) -> Dict[str, torch.Tensor]:
+        """Named views into the workspace of the last `decode_f16(keep_layers=True)`: "trunk.<b>", "blocks.<b>.conv1|conv2|conv3" and
+        "residual" as (B, H, W, channels) float16, "blocks.<b>.gate" as (B, 64) float32 (gdb_decoder_f16_layout)."""
+        kept = getattr(self, "_dec_f16_kept", None)
+        if kept is None:
+            raise ValueError("decode_f16(keep_layers=True) first")
+        B, H, W, L = kept
+        f = GdbFrame()
+        f.B, f.H, f.W = B, H, W
+        n = C.c_int32()
+        _lib.check(self.lib.gdb_decoder_f16_layout(C.byref(self.cfg), C.byref(f), L, _lib.DECF16_KEEP_LAYERS, None, 0, C.byref(n)))
+        regs = (_lib.GdbDecF16Region * n.value)()
+        _lib.check(self.lib.gdb_decoder_f16_layout(C.byref(self.cfg), C.byref(f), L, _lib.DECF16_KEEP_LAYERS, C.cast(regs, C.c_void_p), n.value, C.byref(n)))
+        out = {}
+        for r in regs:
+            dt = torch.float16 if r.dtype == 0 else torch.float32
+            shape = (B, H, W, r.channels) if r.per_pixel else (B, r.channels)
+            nbytes = int(np.prod(shape)) * (2 if r.dtype == 0 else 4)
+            out[r.name.decode()] = self._dec_ws_f16[r.offset:r.offset + nbytes].view(dt).view(shape)
+        return out
 
     @_on_device
     def decode(self, bundle_feat: torch.Tensor, precision: Optional[int] = None) -> torch.Tensor:

@@ -83,6 +83,20 @@ class Network(nn.Module):
                              f"dec_layers {self.dec_layers})")
         if self.shard == "tiles" and self.hot_path != "fused":
             raise ValueError(f"nerf.shard 'tiles' needs nerf.hot_path 'fused' (got {self.hot_path!r}): the operator mirrors render whole frames")
+        # The decoder's arithmetic: "auto" (default, also when absent: fp32 MFMA, or the split-f16 convolutions when `precision` is "f16" /
+        # "f32x" - both fp32-grade) | "f16" (plain f16 MFMA, half-precision activations, the contract of DESIGN.md section 4.10:
+        # HotPathEngine.decode_f16).  "f16" needs bundle_size 2 and the HIP decoder, and does not run by row windows (`shard: tiles`).
+        self.decoder_precision = str(getattr(nrf, "decoder_precision", "auto"))
+        if self.decoder_precision not in ("auto", "f16"):
+            raise ValueError(f"nerf.decoder_precision must be 'auto' or 'f16', got {self.decoder_precision!r}")
+        if self.decoder_precision == "f16":
+            if self.b_size != 2:
+                raise ValueError(f"nerf.decoder_precision 'f16' is built for bundle_size 2 (got {self.b_size})")
+            if not self.hip_decoder:
+                raise ValueError("nerf.decoder_precision 'f16' is a form of the HIP decoder: it needs nerf.hip_decoder and dec_layers 1..16 "
+                                 f"(got hip_decoder {bool(getattr(nrf, 'hip_decoder', True))}, dec_layers {self.dec_layers})")
+            if self.shard == "tiles":
+                raise ValueError("nerf.decoder_precision 'f16' does not run by row windows: nerf.shard 'tiles' keeps the fp32 / split-f16 decoder")
         # The intermediates of a frame (packed render, decoder image) always live in per-engine buffers reused frame after frame.
         # The tensors in the returned dict are fresh by default, as the reference's are (a caller may keep them across frames);
         # `nerf.reuse_outputs: true` makes them per-engine buffers too, overwritten by the next forward: no allocation at all in
@@ -263,7 +277,8 @@ class Network(nn.Module):
                 return {"rgb": img, "nerf_depth": nerf_depth, "mvs_depth": mvs_depth, "opacity": opacity}, mvs_depths, blend_rgbs
             packed = self._render_packed(eng, B, H, W)
             if self.hip_decoder:
-                rgb_c = eng.decode(packed)   # reads channels 3 b^2 .. Q-1 of the packed rows in place
+                # reads channels 3 b^2 .. Q-1 of the packed rows in place
+                rgb_c = eng.decode_f16(packed) if self.decoder_precision == "f16" else eng.decode(packed)
             else:
                 rgb_c = self.upsampler(packed[:, 3 * b * b:eng.Q].view(B, H, W, -1).permute(0, 3, 1, 2)).contiguous().float()
             # N1: pixel-shuffle + add (+ re-weighting) + the two x b upsamplings in one HIP kernel, on the packed rows in place

@@ -433,6 +433,49 @@ int gdb_decode_rows(const GdbConfig* cfg, const GdbFrame* shape, const float* d_
                     const float* d_packed_decoder_weights, int32_t num_layers, int32_t precision, int32_t row_begin, int32_t row_end,
                     int32_t phase, void* d_workspace, size_t workspace_bytes, float* d_rgb_c, void* stream);
 
+/* ---- the decoder on plain f16 MFMA with half-precision activations (ABI v7, added) ---------- */
+/* The same network (bundle_size 2, feat_dim 16, voxel_dim 8, num_layers 1 .. 16) under a narrower, explicit contract: weights f16(w)
+ * (the up stage folded with out_conv in fp64, then rounded once), biases fp32; the 27 input channels read in place from the fp32 rows
+ * and rounded to f16; every convolution f16 x f16 with fp32 accumulate, bias and ReLU in fp32, ONE rounding to f16, stored
+ * channel-last in the workspace; squeeze-excitation sums from conv3's unrounded accumulators, gate in fp32; trunk update
+ * x <- f16(fma(c, gate, x)) and global residual f16(shallow + trunk) materialised; the folded 64 -> 12 convolution writes fp32 d_rgb_c
+ * (B,3,2H,2W).  Deterministic, no atomics on data, workspace contents never matter.  gdb_decode / gdb_decode_rows keep refusing
+ * GDB_PREC_F16: this form has its own packed buffer and entries.
+ *
+ * Packed buffer (gdb_decoder_f16_packed_bytes; h_tensors as for gdb_pack_decoder_weights): a convolution of nct 16-channel output
+ * tiles and nks 32-channel K-steps is nct*nks*9*64*16 bytes, [tile][K-step][tap 9][lane 64][8 halves], element j of lane l =
+ * f16(W[16 tile + (l & 15)][32 kstep + 8 (l >> 4) + j][tap]), zero beyond the layer's channels.  Sections in order: in_conv (nct 4,
+ * nks 1), in_conv.bias (64 floats); per block conv1 (2, 2), conv2 (2, 3), conv3 (4, 4), se.fc.0 (4 x 64 floats), se.fc.2 (64 x 4
+ * floats); the folded up stage (1, 2), channel 3 s + o of sub-pixel s = dy*2 + dx, and its bias (64 floats, 12 used).
+ *
+ * flags: GDB_DECF16_KEEP_LAYERS gives every layer's output, every gate and every trunk a workspace region of its own (without it
+ * two trunk buffers alternate between the blocks and conv1 / conv2 / conv3 / gate regions are shared); d_rgb_c is bit-identical
+ * either way.  gdb_decoder_f16_layout lists the regions (out may be NULL to query *out_count = 5 num_layers + 2): "trunk.<b>"
+ * (b = 0 .. num_layers: the input of block b; trunk.0 = in_conv's output, trunk.<num_layers> = the blocks' output),
+ * "blocks.<b>.conv1" / ".conv2" (32 channels) / ".conv3" (64), "blocks.<b>.gate" (64 floats per batch item: per_pixel 0),
+ * "residual" (= f16(trunk.0 + trunk.<num_layers>), the up stage's input).  Per-pixel regions are (B*H*W, channels) rows.
+ * Refused before the first launch: bundle_size != 2, num_layers outside 1 .. 16, feat_dim / voxel_dim other than 16 / 8, unknown
+ * flags (GDB_E_BADARG); a short row stride or non-positive map (GDB_E_SHAPE); a short workspace (GDB_E_WORKSPACE); NULL pointers. */
+#define GDB_DECF16_KEEP_LAYERS 1
+#define GDB_DECF16_T_F16 0
+#define GDB_DECF16_T_F32 1
+typedef struct GdbDecF16Region {
+    char name[32];
+    uint64_t offset;    /* bytes from the start of the workspace */
+    int32_t channels;
+    int32_t dtype;      /* GDB_DECF16_T_* */
+    int32_t per_pixel;  /* 1: (B*H*W, channels); 0: (B, channels) */
+    int32_t reserved;
+} GdbDecF16Region;
+int gdb_decoder_f16_packed_bytes(const GdbConfig* cfg, int32_t num_layers, size_t* out_bytes);
+int gdb_pack_decoder_weights_f16(const GdbConfig* cfg, int32_t num_layers, const float* const* h_tensors, void* h_out);
+int gdb_decoder_f16_workspace_bytes(const GdbConfig* cfg, const GdbFrame* shape, int32_t num_layers, int32_t flags, size_t* out_bytes);
+int gdb_decoder_f16_layout(const GdbConfig* cfg, const GdbFrame* shape, int32_t num_layers, int32_t flags, GdbDecF16Region* out,
+                           int32_t capacity, int32_t* out_count);
+int gdb_decode_f16(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
+                   const void* d_packed_f16, int32_t num_layers, int32_t flags, void* d_workspace, size_t workspace_bytes,
+                   float* d_rgb_c, void* stream);
+
 /* ---- the cascade's cost-regularisation 3-D U-Nets (ABI v7, added) ---------------------------- */
 /* _UNet3d.forward, networks/gdb_nerf/cost_reg_net.py:24-54, eval mode: depth 2 (CostRegNet_small) or 3 (CostRegNet), in_channels cin
  * (a multiple of 8, <= 256), base_channels (a multiple of 8, base << depth <= 128), out_channels cout = voxel_dim (1 .. 15).  Every

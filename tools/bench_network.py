@@ -20,6 +20,11 @@ for name, opts in {"fused (fp32 MFMA) + hip cost volume + hip decoder [default]"
                    "split-f16 pairs (fp32-grade) in the fused MLP and the decoder + hip cost volume": ["nerf.precision", "f32x"],
                    "fused + hip cost volume, torch decoder": ["nerf.hip_decoder", "False"],
                    "fused f16 operands + hip cost volume + hip decoder": ["nerf.precision", "f16"],
+                   "every switch on, fused f16 operands, split-f16 decoder": ["nerf.precision", "f16", "mvs.hip_cost_reg", "True", "fpn.hip_feature_net", "True",
+                                                                                "mvs.hip_cascade", "True"],
+                   "every switch on, fused f16 operands, f16 decoder (nerf.decoder_precision: f16)": [
+                       "nerf.precision", "f16", "mvs.hip_cost_reg", "True", "fpn.hip_feature_net", "True", "mvs.hip_cascade", "True",
+                       "nerf.decoder_precision", "f16"],
                    "fused, torch cost volume, torch decoder": ["mvs.hip_cost_volume", "False", "nerf.hip_decoder", "False"],
                    "operator mirrors + hip cost volume, torch decoder": ["nerf.hot_path", "mirrors", "nerf.hip_decoder", "False"]}.items():
     torch.manual_seed(0)
