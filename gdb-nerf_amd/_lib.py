@@ -48,6 +48,11 @@ class GdbDecF16Region(C.Structure):
                 ("per_pixel", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GdbDecRegion(C.Structure):
+    """A named fp32 region of the row-window decoder's workspace (gdb_decoder_rows_regions)."""
+    _fields_ = [("name", C.c_char * 16), ("offset", C.c_uint64), ("bytes", C.c_uint64), ("shape", C.c_int32 * 4)]
+
+
 class GdbError(RuntimeError):
     pass
 
@@ -95,6 +100,7 @@ _SIGNATURES = {
     "gdb_decoder_rows_workspace_bytes": (C.c_int, [_CFG, _FRM, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "gdb_decoder_rows_layout": (C.c_int, [_CFG, _FRM, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gdb_decoder_rows_regions": (C.c_int, [_CFG, _FRM, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gdb_decode_rows": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
     "gdb_merge_packed_rows": (C.c_int, [_CFG, _FRM, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gdb_upsample_maps": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, _P, _P]),

@@ -416,14 +416,9 @@ __global__ void __launch_bounds__(256, 5) k_conv16(ConvArgs a) {
     if (a.zero && blockIdx.x == 0 && tid < a.B) a.zero[tid] = 0u;
     F4 acc[NPH][NR];   // D layout: register r of lane l = output row 4 (l >> 4) + r of pixel l & 15
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int co = 16 * mt + 4 * kq + r;
-        const float bv = (a.bias && co < a.cout) ? a.bias[co] : 0.f;
+    for (int p = 0; p < NPH; ++p)
 #pragma unroll
-        for (int p = 0; p < NPH; ++p)
-#pragma unroll
-            for (int q = 0; q < NR; ++q) acc[p][q][r] = bv;
-    }
+        for (int q = 0; q < NR; ++q) acc[p][q] = F4{0.f, 0.f, 0.f, 0.f};
     Stager<TR, 8, VEC, FUSE> st;
     st.init(a, tid, b, x0, y0);
     const int loff0 = (tid >> 3) * DEC_CHS + st.g4;
@@ -471,6 +466,19 @@ __global__ void __launch_bounds__(256, 5) k_conv16(ConvArgs a) {
     }
     // epilogue: lane (pl, kq) holds output channels 16 mt + 4 kq + (0..3) of pixels (y0 + wrow + q, x0 + 16 (ph + p) + pl)
     const int co = 16 * mt + 4 * kq;
+    // The bias goes on LAST, one rounding.  As the chain's first term every product was rounded at the bias's ulp: where the bias
+    // dominates (activations of 1e-3 under a bias of 1e-3) in_conv and the up stage lost ~20 ulp of the output, and the image missed
+    // float64 by 3 x the end-to-end bound (tests/test_decoder_referee.py).
+    if (a.bias) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float bv = co + r < a.cout ? a.bias[co + r] : 0.f;
+#pragma unroll
+            for (int p = 0; p < NPH; ++p)
+#pragma unroll
+                for (int q = 0; q < NR; ++q) acc[p][q][r] += bv;
+        }
+    }
     if (SEP) {   // the segment's channel sums: part[b][y * tilesX + bx][64]; a sum over the 16 lanes of a row group, both pixel halves
 #pragma unroll
         for (int q = 0; q < NR; ++q) {
@@ -522,7 +530,7 @@ __global__ void __launch_bounds__(256, 5) k_conv16(ConvArgs a) {
 // Split-f16 variant (GDB_PREC_F32X).  Workgroup = 4 waves = 4 image rows of one 32-pixel column, all on the SAME 32-channel
 // output tile (a 64-channel layer launches its two tiles as separate workgroups).  Per 16-channel chunk of the input (one MFMA
 // K-step) the workgroup stages in LDS (a) its rows + halo, each pixel's channels as 16 hi halves then 16 lo halves (pixel stride
-// 20 dwords: the 16-byte B-operand reads of a lane group fall on distinct banks), converted from fp32 on the way in, and (b) the
+// 20 dwords: the 16-byte B-operand reads of a lane group fall on distinct banks), split from fp32 on the way in (both halves to nearest), and (b) the
 // chunk's 18 KiB of weight fragments [9 taps][hi, lo][64 lanes][16 B]; a tap is then four ds_read_b128 (A hi / lo, B hi / lo) and
 // three MFMAs.  34 KB of LDS per workgroup: four workgroups per CU, so one's staging runs under the others' MFMAs.  The next
 // chunk's global loads (pixels and weights) are issued before the chunk's MFMAs and converted / stored after them.
@@ -555,12 +563,9 @@ __global__ void __launch_bounds__(256) k_conv3x3x(ConvArgs a) {
     if (a.zero && blockIdx.x == 0 && tid < a.B) a.zero[tid] = 0u;
     f32x16 acc[R];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const float bv = (a.bias && co < a.cout) ? a.bias[co] : 0.f;
+    for (int r = 0; r < 16; ++r)
 #pragma unroll
-        for (int q = 0; q < R; ++q) acc[q][r] = bv;
-    }
+        for (int q = 0; q < R; ++q) acc[q][r] = 0.f;
     Stager<TR, 4, VEC, FUSE> st;
     st.init(a, tid, b, x0, y0);
     const int loff0 = (tid >> 2) * DECX_PXD + (st.g4 >> 1);   // dword offset of slot 0's hi halves in LDS (lo halves 8 dwords further); slot s: 64 pixels on
@@ -583,11 +588,18 @@ __global__ void __launch_bounds__(256) k_conv3x3x(ConvArgs a) {
             if (!st.has(s, tid)) continue;
             const F4 v = st.value(a, s, ch);
             unsigned* dst = lds + loff0 + s * 64 * DECX_PXD;
-            const half2v h01 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(v[0], v[1]));
-            const half2v h23 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(v[2], v[3]));
+            // hi = f16(v), lo = f16(v - hi), both to nearest even (v_cvt_pk_f16_f32) - the split pack_conv_x gives the weights.  Towards
+            // zero (v_cvt_pkrtz) the pair of a value below 2^-3, whose lo is an f16 subnormal, lost up to 2^-24 and always the same way:
+            // at activations of 1e-3 a layer missed its float64 referee by 30 - 40 bounds (tests/test_decoder_referee.py).  The clamp
+            // keeps hi finite beyond the f16 range, as the truncating conversion did.
+            const float c0 = __builtin_amdgcn_fmed3f(v[0], -65504.f, 65504.f), c1 = __builtin_amdgcn_fmed3f(v[1], -65504.f, 65504.f);
+            const float c2 = __builtin_amdgcn_fmed3f(v[2], -65504.f, 65504.f), c3 = __builtin_amdgcn_fmed3f(v[3], -65504.f, 65504.f);
+            const half2v h01 = __builtin_convertvector(F2{c0, c1}, half2v);
+            const half2v h23 = __builtin_convertvector(F2{c2, c3}, half2v);
+            const half2v l01 = __builtin_convertvector(F2{c0 - (float)h01.x, c1 - (float)h01.y}, half2v);
+            const half2v l23 = __builtin_convertvector(F2{c2 - (float)h23.x, c3 - (float)h23.y}, half2v);
             const U2 hi = {__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
-            const U2 lo = {__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v[0] - (float)h01.x, v[1] - (float)h01.y)),
-                           __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v[2] - (float)h23.x, v[3] - (float)h23.y))};
+            const U2 lo = {__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23)};
             *(U2*)dst = hi;
             *(U2*)(dst + 8) = lo;
         }
@@ -620,6 +632,15 @@ __global__ void __launch_bounds__(256) k_conv3x3x(ConvArgs a) {
                 acc[q] = MFMA16(opA[cur][0], opB[cur][q][1], acc[q]);
                 acc[q] = MFMA16(opA[cur][0], opB[cur][q][0], acc[q]);
             }
+        }
+    }
+    if (a.bias) {   // the bias last, one rounding (see k_conv16)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int co = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const float bv = co < a.cout ? a.bias[co] : 0.f;
+#pragma unroll
+            for (int q = 0; q < R; ++q) acc[q][r] += bv;
         }
     }
     const int x = x0 + j;
@@ -816,6 +837,40 @@ extern "C" int gdb_decoder_rows_layout(const GdbConfig* cfg, const GdbFrame* sha
     if (part_row_bytes) *part_row_bytes = sizeof(float) * (size_t)((shape->W + 31) / 32) * DEC_NF;
     if (window_begin) *window_begin = w0;
     if (window_end) *window_end = w1;
+    return GDB_OK;
+}
+
+// The named regions of the row-window workspace (dec_ws) and which P holds each block's input (dec_phases' Px): host arithmetic only.
+extern "C" int gdb_decoder_rows_regions(const GdbConfig* cfg, const GdbFrame* shape, int32_t row_begin, int32_t row_end, int32_t num_layers,
+                                        GdbDecRegion* out, int32_t capacity, int32_t* out_count, int32_t* block_input) {
+    int rc = dec_check_rows(cfg, shape, row_begin, row_end, num_layers); if (rc) return rc;
+    if (!out_count) return gdb_fail(GDB_E_BADARG, "out_count is NULL");
+    *out_count = GDB_DEC_REGIONS;
+    if (block_input)
+        for (int b = 0; b < num_layers; ++b) block_input[b] = b == 0 ? 0 : 1 + ((b - 1) & 1);
+    if (!out) return GDB_OK;
+    if (capacity < GDB_DEC_REGIONS) return gdb_fail(GDB_E_BADARG, "region capacity %d < %d", capacity, GDB_DEC_REGIONS);
+    int w0, w1;
+    dec_window(cfg->bundle_size, num_layers, shape->H, row_begin, row_end, &w0, &w1);
+    const int B = shape->B, Hw = w1 - w0, W = shape->W;
+    const bool up4 = cfg->bundle_size == 4;
+    const DecWs ws = dec_ws(B, Hw, W, cfg->bundle_size, shape->H);
+    int k = 0;
+    auto put = [&](const char* name, size_t off, int d0, int d1, int d2, int d3) {
+        GdbDecRegion& r = out[k++];
+        memset(&r, 0, sizeof r);
+        strncpy(r.name, name, sizeof r.name - 1);
+        r.offset = off;
+        r.shape[0] = d0; r.shape[1] = d1; r.shape[2] = d2; r.shape[3] = d3;
+        r.bytes = sizeof(float) * (size_t)d0 * (size_t)d1 * (size_t)(d2 ? d2 : 1) * (size_t)(d3 ? d3 : 1);
+    };
+    put("P0", ws.P[0], B, Hw, W, DEC_NF); put("P1", ws.P[1], B, Hw, W, DEC_NF); put("P2", ws.P[2], B, Hw, W, DEC_NF);
+    put("Y", ws.Y, B, Hw, W, DEC_NF); put("T", ws.T, B, Hw, W, DEC_NF);
+    put("part", ws.part, B, shape->H, (W + 31) / 32, DEC_NF);
+    put("part2", ws.part2, B, ws.ngrp, DEC_NF, 0);
+    put("gate", ws.gate, B, DEC_NF, 0, 0);
+    put("X", ws.X, up4 ? B : 0, Hw, W, DEC_NF);
+    put("U", ws.U, up4 ? B : 0, 2 * Hw, 2 * W, DEC_NF);
     return GDB_OK;
 }
 

@@ -818,6 +818,25 @@ class DecodeRows:
         b = eng.cfg.bundle_size
         self.rgb_c = torch.empty((f.B, 3, f.H * b, f.W * b), dtype=torch.float32, device=eng.device)
 
+    def activations(self) -> Dict[str, torch.Tensor]:
+        """Named float32 views into `self.ws` (gdb_decoder_rows_regions): "P0", "P1", "P2", "Y", "T" as (B, Hw, W, 64) over the window's
+        Hw rows, "part" as `self.part`, "part2" (B, groups, 64), "gate" (B, 64), at bundle_size 4 also "X" (B, Hw, W, 64) and "U"
+        (B, 2 Hw, 2 W, 64); `self.block_input[b]` names the P that holds block b's input.  Read-only use: nothing is launched."""
+        eng = self.eng
+        f = GdbFrame()
+        f.B, f.H, f.W = self.shape
+        n = C.c_int32()
+        _lib.check(eng.lib.gdb_decoder_rows_regions(C.byref(eng.cfg), C.byref(f), self.r0, self.r1, eng.dec_layers, None, 0, C.byref(n), None))
+        regs, which = (_lib.GdbDecRegion * n.value)(), (C.c_int32 * eng.dec_layers)()
+        _lib.check(eng.lib.gdb_decoder_rows_regions(C.byref(eng.cfg), C.byref(f), self.r0, self.r1, eng.dec_layers, C.cast(regs, C.c_void_p), n.value,
+                                                    C.byref(n), which))
+        self.block_input = [f"P{i}" for i in which]
+        out = {}
+        for r in regs:
+            if r.bytes:
+                out[r.name.decode()] = self.ws[r.offset:r.offset + r.bytes].view(torch.float32).view([d for d in r.shape if d])
+        return out
+
     def run_phase(self, packed: torch.Tensor, phase: int, precision: Optional[int] = None) -> Optional[torch.Tensor]:
         eng = self.eng
         if precision is None:

@@ -408,7 +408,10 @@ int gdb_decoder_workspace_bytes(const GdbConfig* cfg, const GdbFrame* shape, siz
  * 3b² .. Q-1 of every row (network.py:170-174: nerf_feat[:, 3b²:]).  d_rgb_c (B,3,H*b,W*b) = the reference's `rgb_c`; feed it
  * to gdb_merge.  d_workspace: gdb_decoder_workspace_bytes, caller-owned scratch.
  * precision: GDB_PREC_F32 (fp32 MFMA, the reference's arithmetic) or GDB_PREC_F32X (split-f16 operand pairs, fp32 accumulate:
- * fp32-grade, the convolutions' matrix time 5.3x shorter); the packed weights hold both forms. */
+ * fp32-grade, the convolutions' matrix time 5.3x shorter); the packed weights hold both forms.  The decoder's pairs - stored
+ * activations and weights alike - are hi = f16(v), lo = f16(v - hi), both to nearest even (activations clamped to +-65504 first), a
+ * product hi*hi + hi*lo + lo*hi with fp32 accumulate: the operand range of gdb_render_bundles_fused's GDB_PREC_F32X text applies, an
+ * operand below 2^-3 keeps an absolute 2^-25 (DESIGN.md section 4.11 has the contract and its float64 referee). */
 int gdb_decode(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
                const float* d_packed_decoder_weights, int32_t num_layers, int32_t precision, void* d_workspace,
                size_t workspace_bytes, float* d_rgb_c, void* stream);
@@ -432,6 +435,23 @@ int gdb_decoder_rows_layout(const GdbConfig* cfg, const GdbFrame* shape, int32_t
 int gdb_decode_rows(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
                     const float* d_packed_decoder_weights, int32_t num_layers, int32_t precision, int32_t row_begin, int32_t row_end,
                     int32_t phase, void* d_workspace, size_t workspace_bytes, float* d_rgb_c, void* stream);
+/* gdb_decoder_rows_regions (ABI v7, added; host only, launches nothing): the fp32 regions of that workspace, GDB_DEC_REGIONS of them in
+ * this order - "P0", "P1", "P2" (block inputs x_b, (B, Hw, W, 64) over the window's Hw rows; block_input[b], b = 0 .. num_layers-1, is
+ * the index of the P that holds x_b: P0 = in_conv's output and the global residual), "Y" ([x1 | x2] of the block in flight), "T" (its
+ * conv3), "part" ((B, H, ceil(W/32), 64): channel sums of T per frame row and 32-pixel segment), "part2" ((B, groups, 64)), "gate"
+ * ((B, 64)), and at bundle_size 4 "X" ((B, Hw, W, 64): the blocks' output with the last gate and the global residual applied) and "U"
+ * ((B, 2Hw, 2W, 64): the first up stage) - both of zero bytes at bundle_size 2.  shape: unused trailing dimensions are 0.  out may be
+ * NULL to query *out_count; block_input may be NULL.  After phase p of a window equal to the frame the regions hold x_p, Y, T and part
+ * of block p and the gate of block p-1 (after phase num_layers: the last gate, and X / U). */
+#define GDB_DEC_REGIONS 10
+typedef struct GdbDecRegion {
+    char name[16];
+    uint64_t offset;    /* bytes from the start of the workspace */
+    uint64_t bytes;
+    int32_t shape[4];
+} GdbDecRegion;
+int gdb_decoder_rows_regions(const GdbConfig* cfg, const GdbFrame* shape, int32_t row_begin, int32_t row_end, int32_t num_layers,
+                             GdbDecRegion* out, int32_t capacity, int32_t* out_count, int32_t* block_input);
 
 /* ---- the decoder on plain f16 MFMA with half-precision activations (ABI v7, added) ---------- */
 /* The same network (bundle_size 2, feat_dim 16, voxel_dim 8, num_layers 1 .. 16) under a narrower, explicit contract: weights f16(w)
