@@ -5,7 +5,10 @@
 // * Layout: the input is the (N, 3, H, W) image batch, read in place; every intermediate is channel-last (N, h, w, C) in the caller's
 //   workspace; the pyramid levels are written in the module's layout, level 0 (N, out0, H/4, W/4), level 1 (N, out1, H/2, W/2),
 //   level 2 (N, out2, H, W), where every halving is ceil(x / 2) (the 5x5 stride-2 convolutions' padding 2).
-// * Every convolution is one implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulate: a k-ordered fmaf chain):
+// * Every convolution is one implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulate: k-ordered fmaf chains;
+//   a channel-last layer keeps one chain per element e of a lane's E-float load and adds the E of them pairwise at the end, so that
+//   a chain is at most cin / 4 x taps / 4 MFMAs long: one chain over the 864 .. 1600 products of the 96- and 128-channel layers
+//   strayed further from float64 than 4 x the fp32 PyTorch module does, tests/test_fpn_referee.py):
 //   output channels on the MFMA rows, 32 consecutive pixels of one output row on the columns (2 accumulators of 16), K = (tap, input
 //   channel).  One wave owns one 16-row tile.  Operands come straight from global memory (L1 / L2 hits: a pixel's channels are re-read
 //   by the taps of neighbouring waves); the weights are packed on the host in operand order, one E-float load per lane per E k-steps.
@@ -165,9 +168,11 @@ __global__ void __launch_bounds__(256) k_fpn_conv(FpArgs a) {
     const int yg = t % a.nyg;
     const int n = t / a.nyg;
     const int x0 = ct * 16 * NA;
-    F4 acc[NA];
+    F4 part[NA][E];   // one accumulation chain per element of the lane's load
 #pragma unroll
-    for (int i = 0; i < NA; ++i) acc[i] = F4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < NA; ++i)
+#pragma unroll
+        for (int e = 0; e < E; ++e) part[i][e] = F4{0.f, 0.f, 0.f, 0.f};
     const float* wl = a.w + (size_t)mt * a.taps * a.nchunk * 64 * E + (size_t)lane * E;
     if constexpr (IMG) {
         constexpr int TR = ZS == 2 ? 4 : 3, K = 9 * TR;
@@ -182,7 +187,7 @@ __global__ void __launch_bounds__(256) k_fpn_conv(FpArgs a) {
             for (int i = 0; i < NA; ++i) {
                 const int ix = x0 + 16 * i + j + kx - 1;
                 const float b = (rowok && ix >= 0 && ix < a.Wi) ? a.in[rbase + ix] : 0.f;
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, b, acc[i], 0, 0, 0);
+                part[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, b, part[i][0], 0, 0, 0);
             }
         }
     } else {
@@ -215,9 +220,16 @@ __global__ void __launch_bounds__(256) k_fpn_conv(FpArgs a) {
 #pragma unroll
                 for (int e = 0; e < E; ++e)
 #pragma unroll
-                    for (int i = 0; i < NA; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[e], bv[i][e], acc[i], 0, 0, 0);
+                    for (int i = 0; i < NA; ++i) part[i][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[e], bv[i][e], part[i][e], 0, 0, 0);
             }
         }
+    }
+    F4 acc[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        if constexpr (E == 4) acc[i] = (part[i][0] + part[i][1]) + (part[i][2] + part[i][3]);
+        else if constexpr (E == 2) acc[i] = part[i][0] + part[i][1];
+        else acc[i] = part[i][0];
     }
     // epilogue: register r of lane (j, kq) = GEMM row 4 kq + r of column j of accumulator i
     const int row0 = 4 * kq;

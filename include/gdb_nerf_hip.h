@@ -552,7 +552,17 @@ int gdb_cost_reg(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout
  * (GDB_E_WORKSPACE otherwise; its contents do not matter).  With h = ceil(H / 2), q = ceil(h / 2) (and so for W), out: d_level0
  * (N, out0, q, wq), d_level1 (N, out1, h, w), d_level2 (N, out2, H, W); a level's pointer may be NULL exactly when the mask leaves
  * it out.  Only what the mask needs runs: the encoder always, inner1 for levels 1 or 2, inner2 and out2 for level 2.  Every refusal
- * comes before the first launch.  Deterministic (no atomics). */
+ * comes before the first launch.  Deterministic (no atomics).
+ * The workspace is the caller's, and after the call it still holds the intermediates, channel-last (N, rows, columns, channels),
+ * in this order, each region rounded up to a multiple of 64 floats (the padding is never written); the byte count is 4 x the sum:
+ *   A  (N, H, W, c)    conv0.0's output      - only when the mask leaves level 2 out; with level 2 it is written into I2's space
+ *                                              and overwritten there by inner2 (I2 is first written after A is last read)
+ *   F0 (N, H, W, c)    conv0 = conv0.1's output          T1, H1 (N, h, w, 2c)   conv1.0's and conv1.1's outputs
+ *   T2, Q (N, q, wq, 4c)  conv2.0's and conv2.1's outputs
+ *   I1 (N, h, w, 4c)   interpolate(Q) + inner1(H1)       - only with level 1 or 2 in the mask
+ *   I2 (N, H, W, 4c)   interpolate(I1) + inner2(F0)      - only with level 2 in the mask
+ * out0 reads Q, out1 reads I1, out2 reads I2.  A run with mask 3 and one with mask 7 on the same images between them leave every
+ * layer's input and output; the regions they share are bit-identical (tests/test_fpn_referee.py reads them back this way). */
 int gdb_fpn_packed_floats(int32_t base_channels, int32_t out0, int32_t out1, int32_t out2, size_t* out_floats);
 int gdb_pack_fpn_weights(int32_t base_channels, int32_t out0, int32_t out1, int32_t out2, const float* const* h_tensors, float* h_out);
 int gdb_fpn_workspace_bytes(int32_t base_channels, int32_t out0, int32_t out1, int32_t out2, int32_t N, int32_t H, int32_t W,
