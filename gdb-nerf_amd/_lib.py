@@ -27,6 +27,7 @@ DECF16_KEEP_LAYERS = 1   # gdb_decode_f16: every layer output, gate and trunk in
 GDB_OK, GDB_E_BADARG, GDB_E_SHAPE, GDB_E_HIP, GDB_E_WORKSPACE = 0, -1, -2, -3, -4
 GDB_MAX_SAMPLES, GDB_MAX_MIP, GDB_MAX_VIEWS = 16, 3, 8
 GDB_EVAL_IMAGE_REC, GDB_EVAL_DEPTH_REC = 5, 4
+LPIPS_KEEP, LPIPS_TENSORS, LPIPS_REGIONS = 1, 33, 20   # gdb_eval_lpips: flag, host tensors of the packer, regions at most
 
 
 class GdbConfig(C.Structure):
@@ -119,6 +120,11 @@ _SIGNATURES = {
     "gdb_eval_workspace_bytes": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_size_t)]),
     "gdb_eval_image": (C.c_int, [_P, _P, _P] + [C.c_int32] * 7 + [_P, C.c_size_t, _P, C.c_int64, _P]),
     "gdb_eval_depth": (C.c_int, [_P, C.c_int32, C.c_int32, _P] + [C.c_int32] * 4 + [_P, C.c_size_t, _P, C.c_int64, _P]),
+    "gdb_lpips_packed_floats": (C.c_int, [C.POINTER(C.c_size_t)]),
+    "gdb_pack_lpips_weights": (C.c_int, [C.POINTER(_P), _P]),
+    "gdb_lpips_workspace_bytes": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_size_t)]),
+    "gdb_lpips_layout": (C.c_int, [C.c_int32] * 4 + [_P, C.c_int32, C.POINTER(C.c_int32)]),
+    "gdb_eval_lpips": (C.c_int, [_P, _P, _P] + [C.c_int32] * 7 + [_P, C.c_int32, _P, C.c_size_t, _P, C.c_int64, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

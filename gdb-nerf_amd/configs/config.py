@@ -21,7 +21,7 @@ DEFAULTS = {
               "weight_decay": 0.0, "scheduler": {"type": "multi_step", "milestones": [80, 120, 200, 240], "gamma": 0.5}, "batch_size": 4},
     "test": {"batch_size": 1, "collator": "default", "epoch": -1, "batch_sampler": "default",
              "sampler_meta": {"input_views_num": [], "input_views_prob": []}, "eval_depth": False, "eval_center": False,
-             "hip_metrics": False},
+             "hip_metrics": False, "lpips_weights": ""},
 }
 
 

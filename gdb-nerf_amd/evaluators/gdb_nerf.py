@@ -7,12 +7,17 @@ skimage, lpips and cv2 are not in the MI355X image, so the two skimage metrics a
   * structural_similarity(gt, pred, channel_axis=-1) with skimage's defaults for float images:
     7x7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance, data_range 2 (dtype range of
     float images), mean over the interior and the channels                  (reference :86)
-LPIPS needs the `lpips` package and its VGG weights; `eval_lpips: True` without them is an error.
+LPIPS (VGG-16 backbone): with `test.lpips_weights` naming a weights file (torch.save of the mapping `metrics.lpips_weights_from`
+documents; INTEGRATION.md has the export recipe) the definition of include/gdb_nerf_hip.h is restated below in plain torch
+(`lpips_torch`: F.conv2d, from the same weights) and the `lpips` package is never imported.  The package is not available to this
+project: the restatement follows its written definition (release 0.1.4, net='vgg', eval mode, spatial=False), and agreement with the
+package's published weights and values is unverified.  With the key empty `eval_lpips: True` needs the package, and is an error
+without it.
 
 `test.hip_metrics: True` (default off) keeps the frame on the device: with fp32 CUDA prediction and ground truth, `evaluate` only
 enqueues the metric kernels of the HIP library (metrics.py, gdb_eval_image / gdb_eval_depth) and returns; each frame leaves a
 row of float64 sums in a device table that `summarize` copies to the host once.  With the switch off, CPU tensors or non-fp32
-images the numpy path below runs unchanged."""
+images the numpy path below runs unchanged.  With LPIPS weights the device path enqueues gdb_eval_lpips into column 13 of the same row."""
 import math
 import os
 import struct
@@ -21,6 +26,7 @@ from collections import defaultdict
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 from scipy.ndimage import uniform_filter
 
 
@@ -44,6 +50,50 @@ def ssim(gt: np.ndarray, pred: np.ndarray, win: int = 7, data_range: float = 2.0
         s = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
         vals.append(s[pad:-pad, pad:-pad].mean())
     return float(np.mean(vals))
+
+
+# ---- LPIPS (VGG-16) restated in plain torch: the numpy path's arithmetic and the tests' fp32 / float64 reference -------------------
+LPIPS_TAPS = (1, 3, 6, 9, 12)   # the convolutions whose ReLU output is tapped; a 2 x 2 max-pool (floor) follows each but the last
+
+
+def lpips_scale(img: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The input map and the scaling layer: img (N,3,h,w) in [0, 1] -> ((2 img - 1) - shift_c) / scale_c."""
+    return ((img * 2.0 - 1.0) - shift.view(1, 3, 1, 1)) / scale.view(1, 3, 1, 1)
+
+
+def lpips_conv(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """One 3 x 3 convolution with zero padding 1, bias and ReLU."""
+    return F.relu(F.conv2d(x, weight, bias, stride=1, padding=1))
+
+
+def lpips_pool(x: torch.Tensor) -> torch.Tensor:
+    """The 2 x 2 stride-2 max-pool between the groups; floor: an odd last row or column is dropped."""
+    return F.max_pool2d(x, kernel_size=2, stride=2, ceil_mode=False)
+
+
+def lpips_tap(fa: torch.Tensor, fb: torch.Tensor, lin: torch.Tensor) -> torch.Tensor:
+    """One tap: unit-normalise over the channels (eps 1e-10 outside the root), squared difference, the tap's 1 x 1 weights (no bias),
+    mean over the pixels.  fa, fb (N,C,h,w), lin (C,) -> (N,)."""
+    na = torch.sqrt(torch.sum(fa ** 2, dim=1, keepdim=True)) + 1e-10
+    nb = torch.sqrt(torch.sum(fb ** 2, dim=1, keepdim=True)) + 1e-10
+    d = F.conv2d((fa / na - fb / nb) ** 2, lin.view(1, -1, 1, 1))
+    return d.mean(dim=(2, 3))[:, 0]
+
+
+def lpips_torch(a: torch.Tensor, b: torch.Tensor, weights) -> torch.Tensor:
+    """LPIPS of the image batches a, b (N,3,h,w), values in [0, 1], from `weights` (metrics.lpips_weights_from's mapping, in the
+    images' dtype and on their device): (N,) values.  The same chain, term by term, as the HIP library's gdb_eval_lpips."""
+    with torch.no_grad():
+        x = lpips_scale(torch.cat([a, b]), weights["shift"], weights["scale"])
+        total, tap = 0.0, 0
+        for i in range(13):
+            x = lpips_conv(x, weights[f"conv.{i}.weight"], weights[f"conv.{i}.bias"])
+            if i == LPIPS_TAPS[tap]:
+                total = total + lpips_tap(x[:len(a)], x[len(a):], weights[f"lin.{tap}"])
+                tap += 1
+                if tap < len(LPIPS_TAPS):
+                    x = lpips_pool(x)
+        return total
 
 
 def _resize_bilinear(img: np.ndarray, size_hw) -> np.ndarray:
@@ -72,8 +122,8 @@ def write_png(path: str, rgb_u8: np.ndarray) -> None:
 
 class Evaluator:
     # columns of a frame's row in the device table: the image record, then the depth records of the NeRF and the MVS depth
-    _COLS = 16   # 5 + 4 + 4, padded to whole 128-byte rows
-    _NERF_DEPTH, _MVS_DEPTH = 5, 9
+    _COLS = 16   # 5 + 4 + 4 + 1, padded to whole 128-byte rows
+    _NERF_DEPTH, _MVS_DEPTH, _LPIPS = 5, 9, 13
 
     def __init__(self, cfg):
         self.cfg = cfg
@@ -81,7 +131,12 @@ class Evaluator:
         self.hip_metrics = bool(getattr(cfg.test, "hip_metrics", False))
         self._table, self._rows = None, []   # device rows (capacity, _COLS) and per row on the host (scene, SSIM windows, has depth)
         self.loss_fn_vgg = None
-        if getattr(cfg, "eval_lpips", False):
+        self.lpips_weights, self._lpips_on = None, {}   # the 33 CPU tensors; per device: (the weights there, the packed buffer)
+        path = getattr(cfg.test, "lpips_weights", "")
+        if getattr(cfg, "eval_lpips", False) and path:  # caller-supplied weights: the `lpips` package is never imported
+            from .. import metrics
+            self.lpips_weights = metrics.lpips_weights_from(torch.load(path, map_location="cpu", weights_only=True))
+        elif getattr(cfg, "eval_lpips", False):
             try:
                 import lpips  # noqa: F401
             except ImportError as e:
@@ -96,6 +151,19 @@ class Evaluator:
     def _reset(self):
         self.psnrs, self.ssims, self.lpips = [], [], []
         self.scene = defaultdict(lambda: defaultdict(list))
+
+    def _lpips_weights_on(self, device, packed=False):
+        """The LPIPS weights on `device` (cached), or their packed buffer for gdb_eval_lpips (packed once per device, on the host)."""
+        device = torch.device(device)
+        ent = self._lpips_on.setdefault(device, [None, None])
+        if packed:
+            if ent[1] is None:
+                from .. import metrics
+                ent[1] = metrics.pack_lpips(self.lpips_weights, device)
+            return ent[1]
+        if ent[0] is None:
+            ent[0] = {k: v.to(device) for k, v in self.lpips_weights.items()}
+        return ent[0]
 
     def use_hip_metrics(self, output, batch) -> bool:
         """The switch is on, and prediction, ground truth (fp32) and mask are CUDA tensors."""
@@ -116,7 +184,8 @@ class Evaluator:
 
     def _evaluate_hip(self, output, batch):
         """The device path of `evaluate`: enqueue and return.  No host copy, no `.item()`, no synchronising call — except for
-        `save_result`, whose PNG is written from a host copy (that copy waits for the stream), and `eval_lpips`, whose `.item()` does.
+        `save_result`, whose PNG is written from a host copy (that copy waits for the stream), and `eval_lpips` through the `lpips`
+        package, whose `.item()` does (with `test.lpips_weights` LPIPS is enqueued like the rest: column 13 of the frame's row).
         An image too small for one 7 x 7 window raises ValueError (skimage raises there too; the numpy path returns NaN with a
         warning)."""
         from .. import metrics
@@ -131,6 +200,8 @@ class Evaluator:
             crop = (ch, cw, max(h - 2 * ch, 0) if ch else 0, max(w - 2 * cw, 0) if cw else 0)
         rows = self._next_rows(B, gt.device)
         metrics.eval_image(pred, gt, mask, rows, crop)
+        if self.lpips_weights is not None:
+            metrics.eval_lpips(pred, gt, mask, self._lpips_weights_on(gt.device, packed=True), rows[:, self._LPIPS:], crop)
         if getattr(self.cfg, "save_result", False) or self.loss_fn_vgg is not None:
             pc = pred.permute(0, 2, 3, 1).clamp(0.0, 1.0)[:, crop[0]:crop[0] + crop[2], crop[1]:crop[1] + crop[3]]
             keep = (mask >= 1)[:, crop[0]:crop[0] + crop[2], crop[1]:crop[1] + crop[3], None]
@@ -152,7 +223,7 @@ class Evaluator:
                                    row[:, self._NERF_DEPTH:], resize=True)
                 metrics.eval_depth(output["mvs_depth"][b:b + 1].detach().float(), batch["tar_gt_ms"]["depth"][-1][b:b + 1].float(),
                                    row[:, self._MVS_DEPTH:], resize=False)
-            self._rows.append((scene, (crop[2] - 6) * (crop[3] - 6), depth))
+            self._rows.append((scene, (crop[2] - 6) * (crop[3] - 6), depth, self.lpips_weights is not None))
 
     @property
     def capacity(self) -> int:
@@ -166,13 +237,16 @@ class Evaluator:
             return
         table = self._table[:len(self._rows)].cpu().numpy()
         with np.errstate(divide="ignore", invalid="ignore"):
-            for (scene, windows, depth), r in zip(self._rows, table):
+            for (scene, windows, depth, has_lpips), r in zip(self._rows, table):
                 mse = float(r[0] / (3.0 * r[1]))
                 row = {"psnr": float("inf") if mse == 0 else 10.0 * math.log10(1.0 / mse),
                        "ssim": float(np.mean(r[2:5] / windows))}
                 for k, v in row.items():
                     getattr(self, k + "s").append(v)
                     self.scene[scene][k].append(v)
+                if has_lpips:
+                    self.lpips.append(float(r[self._LPIPS]))
+                    self.scene[scene]["lpips"].append(float(r[self._LPIPS]))
                 if depth:
                     for tag, o in (("", self._NERF_DEPTH), ("mvs_", self._MVS_DEPTH)):
                         for k, i in (("abs", 0), ("acc_2", 1), ("acc_10", 2)):
@@ -198,8 +272,11 @@ class Evaluator:
             g, p = gt[b].copy(), pred[b].copy()
             g[~m], p[~m] = 0.0, 0.0
             row = {"psnr": psnr(g[m], p[m], 1.0), "ssim": ssim(g, p)}
-            if self.loss_fn_vgg is not None:
-                import torch
+            if self.lpips_weights is not None:   # the plain-torch restatement, on the device the frame came on
+                dev = output["rgb"].device
+                t = lambda a: torch.from_numpy(a)[None].permute(0, 3, 1, 2).contiguous().float().to(dev)   # fp32 like the weights, whatever the frame was
+                row["lpips"] = lpips_torch(t(p), t(g), self._lpips_weights_on(dev))[0].item()
+            elif self.loss_fn_vgg is not None:
                 t = lambda a: (torch.from_numpy(a)[None].permute(0, 3, 1, 2) - 0.5) * 2.0
                 row["lpips"] = self.loss_fn_vgg(t(g).cuda(), t(p).cuda()).item()
             for k, v in row.items():
@@ -219,7 +296,7 @@ class Evaluator:
     def summarize(self):
         self.collect()
         ret = {"psnr": np.mean(self.psnrs), "ssim": np.mean(self.ssims)}
-        if self.loss_fn_vgg is not None:
+        if self.loss_fn_vgg is not None or self.lpips_weights is not None:
             ret["lpips"] = np.mean(self.lpips)
         print("=" * 30)
         for scene, rows in self.scene.items():

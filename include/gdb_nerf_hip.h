@@ -598,6 +598,49 @@ int gdb_eval_image(const float* d_pred, const float* d_gt, const float* d_mask, 
 int gdb_eval_depth(const float* d_depth, int32_t Hd, int32_t Wd, const float* d_gt, int32_t B, int32_t H, int32_t W, int32_t resize,
                    void* d_workspace, size_t ws_bytes, double* d_records, int64_t record_stride, void* stream);
 
+/* ---- LPIPS with the VGG-16 backbone, from caller-supplied weights (ABI v7, added) --------------------------------------------
+ * lpips.LPIPS(net='vgg') in eval mode, spatial=False, as of release 0.1.4, restated (the package is not available to this project: the
+ * definition here is the contract, and agreement with the package's published weights and values is unverified).  For two images a, b
+ * with values in [0, 1], shape (3, h, w):
+ *   1. scaling layer: x = ((2 img - 1) - shift_c) / scale_c per channel (the package's shift [-.030, -.088, -.188], scale [.458, .448, .450]);
+ *   2. thirteen 3 x 3 convolutions, stride 1, with bias and ReLU, zero padding 1 applied to the SCALED input; channels 3->64, 64->64 |
+ *      64->128, 128->128 | 128->256, 256->256 x 2 | 256->512, 512->512 x 2 | 512->512 x 3; a 2 x 2 stride-2 max-pool between the groups,
+ *      floor (an odd last row or column is dropped);
+ *   3. taps: the five group outputs after ReLU and before the pool (relu1_2, 2_2, 3_3, 4_3, 5_3);
+ *   4. per tap l and pixel: n = sqrt(sum_c f_c^2) + 1e-10 (the eps outside the root), d = sum_c w_lc (fa_c / na - fb_c / nb)^2 with the
+ *      tap's 1 x 1 weights w_l (C_l values, no bias); t_l = the mean of d over the tap's pixels;
+ *   5. LPIPS = sum_l t_l.
+ * Per-pixel terms in fp32 (convolutions on fp32 MFMA: exact products, fp32 accumulate), sums over pixels and taps in fp64 in a fixed
+ * order: deterministic, no atomics, the workspace's previous contents do not matter, and an image's value does not depend on its
+ * batch position.  Nothing syncs with the host; the library allocates nothing.
+ *
+ * gdb_pack_lpips_weights (host side): h_tensors = 13 convolution weights (cout, cin, 3, 3), their 13 biases, the 5 tap weights (C_l
+ * floats), shift (3), scale (3): GDB_LPIPS_TENSORS host pointers, none NULL (GDB_E_BADARG).  Packed buffer (gdb_lpips_packed_floats),
+ * every block at a multiple of 64 floats: [shift 3 | scale 3]; conv.0 weights [mt 4][step 7][lane 64] = W[16 mt + (lane & 15)][k = 4 step
+ * + (lane >> 4)], k = (ci 3 + ky) 3 + kx, zero at k = 27, and its bias; conv.i weights [mp cout / 32][tap 9][cc cin / 16][m 2][lane 64][e 4]
+ * = W[32 mp + 16 m + (lane & 15)][16 cc + 4 (lane >> 4) + e][tap = ky 3 + kx], and its bias; then the five tap weights.
+ *
+ * gdb_eval_lpips: d_pred (B, 3, H, W), d_gt (B, H, W, 3), d_mask (B, H, W), read in place as gdb_eval_image reads them: the crop, the
+ * clamp of d_pred to [0, 1], both images zeroed except where mask >= 1 (the evaluator's rule: a NaN mask value counts as masked; image value 0, i.e. -1 before the scaling layer) and the scaling
+ * layer are applied by the first convolution on load.  Writes ONE double per batch item at d_records + b * record_stride.
+ * Activations are channel-last fp32 (2 B, rows, columns, channels): image n < B is d_pred of item n, image B + n is d_gt of item n.
+ * flags 0: two activation buffers alternate.  GDB_LPIPS_KEEP: the scaled input, every convolution's output and the four pooled maps
+ * each keep a region of their own; the record is bit-identical either way.  gdb_lpips_layout lists the regions of a workspace (h, w:
+ * the cropped extent; out may be NULL to query *out_count): with GDB_LPIPS_KEEP "scaled", then "conv.0", "conv.1", "pool.0", "conv.2",
+ * ... "conv.12" in the order they are written, else "ping", "pong"; then "taps" ((B, 5) doubles: the t_l) and "partials" (doubles).
+ * Refused before any launch: a NULL pointer, unknown flags or a record_stride < 1 (GDB_E_BADARG); B, H or W < 1, a crop outside the
+ * image, a cropped extent below 16 rows or columns - the fifth tap would be empty (GDB_E_SHAPE); a short workspace (GDB_E_WORKSPACE). */
+#define GDB_LPIPS_KEEP 1
+#define GDB_LPIPS_TENSORS 33
+#define GDB_LPIPS_REGIONS 20
+int gdb_lpips_packed_floats(size_t* out_floats);
+int gdb_pack_lpips_weights(const float* const* h_tensors, float* h_out);
+int gdb_lpips_workspace_bytes(int32_t B, int32_t h, int32_t w, int32_t flags, size_t* out_bytes);
+int gdb_lpips_layout(int32_t B, int32_t h, int32_t w, int32_t flags, GdbDecRegion* out, int32_t capacity, int32_t* out_count);
+int gdb_eval_lpips(const float* d_pred, const float* d_gt, const float* d_mask, int32_t B, int32_t H, int32_t W, int32_t crop_y0,
+                   int32_t crop_x0, int32_t crop_h, int32_t crop_w, const float* d_packed, int32_t flags, void* d_workspace,
+                   size_t workspace_bytes, double* d_records, int64_t record_stride, void* stream);
+
 /* ---- one cascade MVS stage as one call (ABI v7, added) ------------------------------------------------------------------------
  * One stage of DepthNet.forward (networks/gdb_nerf/depth_net.py:133-156): camera set-up, plane sweep, the stage's U-Net, softmax
  * over D and depth regression.  Nothing syncs with the host; deterministic (no atomics); the caller owns all memory.

@@ -50,8 +50,9 @@ def wall(fn, iters, warmup, sync):
     return {"median_ms": round(float(np.median(ts)), 4), "min_ms": round(float(ts.min()), 4), "max_ms": round(float(ts.max()), 4)}
 
 
-def loop_fps(hip, frames):
-    """Network.forward + evaluate per frame, one summarize at the end: wall clock from the first forward to summarize's return."""
+def loop_fps(hip, frames, make_ev=None):
+    """Network.forward + evaluate per frame, one summarize at the end: wall clock from the first forward to summarize's return.
+    `make_ev(hip)`: another evaluator factory than `evaluator` (tools/bench_lpips.py: LPIPS on)."""
     fr = synthetic.make_frame(512, 640, V=3, seed=0)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     torch.manual_seed(0)
@@ -62,7 +63,7 @@ def loop_fps(hip, frames):
                            "mask": torch.ones(1, 512, 640).cuda()},
              "near_far": t(fr["near_far"]),
              "meta": {"scene": ["scan1"], "tar_view": torch.zeros(1, dtype=torch.long), "frame_id": torch.zeros(1, dtype=torch.long)}}
-    ev = evaluator(hip)
+    ev = (make_ev or evaluator)(hip)
     out = []
     with torch.no_grad():
         for rep in range(3):   # the first repetition warms MIOpen, the library and the allocator; the median of the rest is reported
