@@ -1,25 +1,19 @@
-// Production kernel: the whole hot-path section of Network.forward (network.py:145-169 of the
-// reference: build_rays → sample → encode → NeRF MLP → normalised alpha composite) in ONE
-// launch, with no per-sample intermediate in HBM.
-//
-// Mapping (gfx950, wave64):
-//   workgroup  = one 32-bundle segment of a bundle-map row; wave w handles sample slots
-//                k = w, w+nw, ... of those bundles (one slot per wave when S_max fits).
-//   lane       = (j = lane&31: bundle of the segment, h = lane>>5: "half").  The two halves
-//                of a wave split every per-sample vector exactly the way the 32x32 MFMA
-//                accumulator splits its rows: half h owns rows 4h..4h+3 of every 8.
-//   gather     = coalesced along the row: the NCDHW cost volume and the NCHW images are read
-//                along x by consecutive lanes; feature texels (20 floats, channel-last
-//                pyramid) are read as 16-B chunks, chunk parity = h.
-//   MLP        = every layer is D = W · Xᵀ on v_mfma_f32_32x32x16_f16 (samples on the MFMA
-//                column = lane, features on the accumulator rows).  A layer's accumulator is
-//                converted in place to the next layer's B operand (weights are pre-permuted
-//                on the host to the accumulator's row order), so activations never leave
-//                registers; views are separate accumulators of the same 32 samples, which
-//                makes variance/mean/softmax over views per-lane arithmetic.
-//   composite  = per-slot results meet in LDS; transmittance weights, normalisation and the
-//                weighted sum run per bundle; the (N_b, 39) output rows are written as one
-//                contiguous run per segment.
+// Production kernels: the whole hot-path section of Network.forward (network.py:145-169 of the reference: build_rays -> sample ->
+// encode -> NeRF MLP -> normalised alpha composite) in ONE launch, with no per-sample intermediate in HBM.  gfx950, wave64; everywhere
+// lane = (j = lane & 31: sample or bundle, h = lane >> 5: the half that owns rows 4h..4h+3 of every 8 of the 32x32 MFMA accumulator).
+// Map of the file, in order:
+//   packing     - layout of the packed weights (MFMA A-operand fragments, fp32 tables) and their host packer (gdb_pack_mfma_section).
+//   cores       - FusedArgs; the gather of a sample's inputs (cost volume, images, feature pyramid: coalesced along the row) and the
+//                 MLP cores per precision: every layer D = W x X^T on MFMA, a layer's accumulator converted in place to the next
+//                 layer's B operand, views as separate accumulators (variance / mean / softmax over views are per-lane arithmetic).
+//   kernels     - the four schedules: k_render_fused (slot waves: workgroup = one 32-bundle segment, one sample slot per wave, composite
+//                 through LDS), k_render_solo (segment wave: one wave walks all slots), k_render_dense / k_render_flat (the compacted
+//                 sample list cut into windows of whole bundles / of exactly 32 samples: ONE body, render_list_body).
+//   list lookup - list_counts / list_total / list_fill: a wave's tiles of the walk, looked up once; the flat schedule's hand-off of a
+//                 bundle that straddles two windows (store_sc1_16, flat_fix_boundary, flat_settle).
+//   launchers   - launch_fused / launch_solo; for the list schedules lds_waves_per_cu, list_launches, list_grid, launch_list_n /
+//                 launch_list, ensure_list_plan, list_waves_per_simd / launch_list_wps; k_bundle_colours (bundle_size 1 / 4).
+//   entries     - resolve_schedule, render_launch / render_center_launch, gdb_render_info, gdb_render_bundles_fused / _packed.
 #include "gdb_internal.h"
 #if !defined(GDB_DIAG) && (defined(GDB_XP_NOW) || defined(GDB_XP_PK))
 #error "GDB_XP_* timing experiments produce wrong results by design: they exist in the diagnostic build (-DGDB_DIAG) only"
@@ -2147,71 +2141,80 @@ __device__ __forceinline__ float wave_shr1(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
 }
 // Persistent tiles (round 4).  The launch is exactly the resident grid - as many workgroups as the chip holds at once (CUs x the
-// workgroups LDS and registers admit per CU, launch_dense_n) - and every wave WALKS tiles: XCD x owns the contiguous band
+// workgroups LDS and registers admit per CU, launch_list_n) - and every wave WALKS tiles: XCD x owns the contiguous band
 // [x chunk, (x + 1) chunk) of the dense tile numbering, and the wave in slot s of that XCD renders tiles x chunk + s, + stride,
 // + 2 stride, ... (stride = the XCD's wave slots).  Static, so deterministic; no atomics, no cross-workgroup dependency; row
 // strips and batch items (grid y) stay bit-exact because a tile is still one window of one row.  Against one workgroup per tile
 // (round 3) no wave slot waits for the dispatcher between two tiles: the occupancy trace of that form showed the launch drop from
 // 3.0 to 2.05 resident waves per SIMD when the first round of workgroups ended together (profiles/r03/stamps_f32_schedule3.txt).
-// Tiles are numbered densely over the windows IN USE (plan_row leaves the count per row in WsLayout::nwinOff); a wave turns a
-// tile index into (row, window) with one scan of those counts - four rows per lane, 256 rows per round - restricted to the rows
-// [rlo, rhi) this launch renders.  Everything comes out wave-uniform.
-__device__ __forceinline__ int4 dense_counts(const DevFrame& f, int rlo, int rhi, int c0, int lane, int& s4) {
-    // this lane's four rows of round c0: clamped to what the plan was sized for, zero outside the strip
-    const int q0 = rlo >> 2, nq = ((rhi + 3) >> 2) - q0;  // int4s of the count array that touch the strip
-    const int q = c0 + lane;
-    int4 n = make_int4(0, 0, 0, 0);
-    if (q < nq) n = ((const int4*)f.nwin)[q0 + q];
-    const int r4 = (q0 + q) << 2;
-    n.x = (r4 + 0 >= rlo && r4 + 0 < rhi) ? min(max(n.x, 0), f.planMW) : 0;
-    n.y = (r4 + 1 >= rlo && r4 + 1 < rhi) ? min(max(n.y, 0), f.planMW) : 0;
-    n.z = (r4 + 2 >= rlo && r4 + 2 < rhi) ? min(max(n.z, 0), f.planMW) : 0;
-    n.w = (r4 + 3 >= rlo && r4 + 3 < rhi) ? min(max(n.w, 0), f.planMW) : 0;
-    s4 = n.x + n.y + n.z + n.w;
-    return n;
-}
+// Tiles are numbered densely over what the plan holds: FLAT = false, the windows IN USE (plan_row leaves the count per row in
+// WsLayout::nwinOff), one tile per count; FLAT = true, the samples (WsLayout::nsampOff), one tile per 32 counts.  A wave turns a
+// tile index into (row, offset inside the row) with one scan of those counts - four rows per lane, 256 rows per round - restricted
+// to the rows [rlo, rhi) this launch renders.  Everything comes out wave-uniform.
 __device__ __forceinline__ int wave_scan_incl(int v, int lane) {  // inclusive prefix over the 64 lanes
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(v, d); if (lane >= d) v += u; }
     return v;
 }
-// live tiles of the rows [rlo, rhi)
-__device__ __forceinline__ int dense_total(const DevFrame& f, int rlo, int rhi, int lane) {
+// this lane's four rows of round c0: clamped to what the plan was sized for (dense: planMW windows; flat: a row's list holds at most
+// W S_max <= smapStride - 32 entries), zero outside the strip
+template <bool FLAT>
+__device__ __forceinline__ int4 list_counts(const DevFrame& f, int rlo, int rhi, int c0, int lane, int& s4) {
+    const int q0 = rlo >> 2, nq = ((rhi + 3) >> 2) - q0;  // int4s of the count array that touch the strip
+    const int q = c0 + lane;
+    int4 n = make_int4(0, 0, 0, 0);
+    if (q < nq) n = ((const int4*)(FLAT ? f.nsamp : f.nwin))[q0 + q];
+    const int r4 = (q0 + q) << 2, cap = FLAT ? f.smapStride - 32 : f.planMW;
+    n.x = (r4 + 0 >= rlo && r4 + 0 < rhi) ? min(max(n.x, 0), cap) : 0;
+    n.y = (r4 + 1 >= rlo && r4 + 1 < rhi) ? min(max(n.y, 0), cap) : 0;
+    n.z = (r4 + 2 >= rlo && r4 + 2 < rhi) ? min(max(n.z, 0), cap) : 0;
+    n.w = (r4 + 3 >= rlo && r4 + 3 < rhi) ? min(max(n.w, 0), cap) : 0;
+    s4 = n.x + n.y + n.z + n.w;
+    return n;
+}
+// counts of the rows [rlo, rhi): live windows (dense) or samples (flat)
+template <bool FLAT>
+__device__ __forceinline__ int list_total(const DevFrame& f, int rlo, int rhi, int lane) {
     const int nq = ((rhi + 3) >> 2) - (rlo >> 2);
     int T = 0;
     for (int c0 = 0; c0 < nq; c0 += 64) {
-        int s; dense_counts(f, rlo, rhi, c0, lane, s);
+        int s; list_counts<FLAT>(f, rlo, rhi, c0, lane, s);
         T += __shfl(wave_scan_incl(s, lane), 63);
     }
     return T;
 }
 // This wave's tiles - slot `slot` of XCD `xcd`: tiles xcd chunk + slot, + stride, ... inside the XCD's band [xcd chunk, (xcd + 1) chunk),
-// chunk = ceil(T / 8), at most 64 of them (the launcher sizes the grid so) - as descriptors row << 16 | window, one per LANE of a
-// single register: the scan of the per-row window counts runs once per wave, a tile of the walk then costs one v_readlane.
-// (Looked up per tile - a reload of the counts, a 6-step scan, a ballot - it was ~150 vector instructions per tile, 4 % of the
-// wave's, read off the ISA.)  Returns the number of descriptors written; rows are the global row index (< 65536, checked by the
-// launcher), windows < planMW <= 65535.
-__device__ __forceinline__ int dense_fill(const DevFrame& f, int rlo, int rhi, int lane, int xcd, int slot, int stride, unsigned& vdesc) {
+// chunk = ceil(T / 8), at most 64 of them (the launcher sizes the grid so) - as descriptors row << 16 | offset (dense: the window; flat:
+// the tile's first sample inside its first row), one per LANE of a single register: the scan of the per-row counts runs once per wave,
+// a tile of the walk then costs one v_readlane.  (Looked up per tile - a reload of the counts, a 6-step scan, a ballot - it was ~150
+// vector instructions per tile, 4 % of the wave's, read off the ISA.)  Returns the number of descriptors written; rows are the global
+// row index (< 65536, checked by the launcher), offsets < 65536 (planMW, W S_max: likewise).  flat: t0_out = the wave's first tile's
+// index in the launch.
+template <bool FLAT>
+__device__ __forceinline__ int list_fill(const DevFrame& f, int rlo, int rhi, int lane, int xcd, int slot, int stride, unsigned& vdesc, int& t0_out) {
+    constexpr int UNIT = FLAT ? 32 : 1;   // counts per tile
     const int q0 = rlo >> 2, nq = ((rhi + 3) >> 2) - q0;
     int s4;
-    int4 n = dense_counts(f, rlo, rhi, 0, lane, s4);
+    int4 n = list_counts<FLAT>(f, rlo, rhi, 0, lane, s4);
     int incl = wave_scan_incl(s4, lane);
     // the total: this round's for strips of up to 256 rows (every BASELINE bundle map but c3 / c4 / c5), else one more pass over the counts
-    const int T = nq <= 64 ? __builtin_amdgcn_readlane(incl, 63) : __builtin_amdgcn_readfirstlane(dense_total(f, rlo, rhi, lane));
+    const int N = nq <= 64 ? __builtin_amdgcn_readlane(incl, 63) : __builtin_amdgcn_readfirstlane(list_total<FLAT>(f, rlo, rhi, lane));
+    const int T = FLAT ? (N + 31) >> 5 : N;
     const int chunk = (T + 7) >> 3, t0 = xcd * chunk + slot, tend = min(T, (xcd + 1) * chunk);
+    if constexpr (FLAT) t0_out = t0;
     int run = 0, i = 0;
     vdesc = 0xFFFFFFFFu;
     for (int c0 = 0; c0 < nq && i < 64; c0 += 64) {
-        if (c0) { n = dense_counts(f, rlo, rhi, c0, lane, s4); incl = wave_scan_incl(s4, lane); }
+        if (c0) { n = list_counts<FLAT>(f, rlo, rhi, c0, lane, s4); incl = wave_scan_incl(s4, lane); }
         const int tot = __builtin_amdgcn_readlane(incl, 63);
-        for (; i < 64; ++i) {   // this wave's tiles that fall into the rows of this round
+        for (; i < 64; ++i) {   // this wave's tiles that begin in the rows of this round
             const int t = t0 + i * stride;
-            if (t >= tend || t - run >= tot) break;
-            const int tl = t - run;
-            const int ls = __builtin_ctzll(__ballot(tl < incl));  // the lane whose four rows hold the tile
+            if (t >= tend || UNIT * t - run >= tot) break;
+            const int gl = UNIT * t - run;                          // offset of the tile's first count inside this round
+            const int ls = __builtin_ctzll(__ballot(gl < incl));   // the lane whose four rows hold it
             const int ex = __builtin_amdgcn_readlane(incl - s4, ls);
             const int nx = __builtin_amdgcn_readlane(n.x, ls), ny = __builtin_amdgcn_readlane(n.y, ls), nz = __builtin_amdgcn_readlane(n.z, ls);
-            int r = (q0 + c0 + ls) << 2, rem = tl - ex;
+            int r = (q0 + c0 + ls) << 2, rem = gl - ex;
             if (rem >= nx) { rem -= nx; ++r; if (rem >= ny) { rem -= ny; ++r; if (rem >= nz) { rem -= nz; ++r; } } }
             if (lane == i) vdesc = ((unsigned)r << 16) | ((unsigned)rem & 0xFFFFu);   // (a v_cndmask on a wave-uniform value)
         }
@@ -2235,61 +2238,7 @@ __device__ __forceinline__ int dense_fill(const DevFrame& f, int rlo, int rhi, i
 // bit-identical to the full render and to GDB_SCHED_DENSE.  (Until round 5 a second launch, k_flat_fix, did that: 5 us of launch
 // ramp and two dependent memory round trips behind every render.)
 // A window may also span bundle-map rows (the row of a lane is per-lane; a row holds >= W samples, so two rows in all but tiny maps).
-// Tiles are looked up once per wave like the dense schedule's: descriptor = first row << 16 | sample offset inside that row.
-__device__ __forceinline__ int4 flat_counts(const DevFrame& f, int rlo, int rhi, int c0, int lane, int& s4) {
-    const int q0 = rlo >> 2, nq = ((rhi + 3) >> 2) - q0;
-    const int q = c0 + lane;
-    int4 n = make_int4(0, 0, 0, 0);
-    if (q < nq) n = ((const int4*)f.nsamp)[q0 + q];
-    const int r4 = (q0 + q) << 2, cap = f.smapStride - 32;   // (a row's list holds at most W S_max <= smapStride - 32 entries)
-    n.x = (r4 + 0 >= rlo && r4 + 0 < rhi) ? min(max(n.x, 0), cap) : 0;
-    n.y = (r4 + 1 >= rlo && r4 + 1 < rhi) ? min(max(n.y, 0), cap) : 0;
-    n.z = (r4 + 2 >= rlo && r4 + 2 < rhi) ? min(max(n.z, 0), cap) : 0;
-    n.w = (r4 + 3 >= rlo && r4 + 3 < rhi) ? min(max(n.w, 0), cap) : 0;
-    s4 = n.x + n.y + n.z + n.w;
-    return n;
-}
-// samples of the rows [rlo, rhi)
-__device__ __forceinline__ int flat_total(const DevFrame& f, int rlo, int rhi, int lane) {
-    const int nq = ((rhi + 3) >> 2) - (rlo >> 2);
-    int T = 0;
-    for (int c0 = 0; c0 < nq; c0 += 64) {
-        int s; flat_counts(f, rlo, rhi, c0, lane, s);
-        T += __shfl(wave_scan_incl(s, lane), 63);
-    }
-    return T;
-}
-// This wave's tiles (slot `slot` of XCD `xcd`, as dense_fill) -> descriptors, one per lane; t0 = its first tile's index in the launch.
-__device__ __forceinline__ int flat_fill(const DevFrame& f, int rlo, int rhi, int lane, int xcd, int slot, int stride, unsigned& vdesc, int& t0_out) {
-    const int q0 = rlo >> 2, nq = ((rhi + 3) >> 2) - q0;
-    int s4;
-    int4 n = flat_counts(f, rlo, rhi, 0, lane, s4);
-    int incl = wave_scan_incl(s4, lane);
-    const int NS = nq <= 64 ? __builtin_amdgcn_readlane(incl, 63) : __builtin_amdgcn_readfirstlane(flat_total(f, rlo, rhi, lane));
-    const int T = (NS + 31) >> 5;
-    const int chunk = (T + 7) >> 3, t0 = xcd * chunk + slot, tend = min(T, (xcd + 1) * chunk);
-    t0_out = t0;
-    int run = 0, i = 0;
-    vdesc = 0xFFFFFFFFu;
-    for (int c0 = 0; c0 < nq && i < 64; c0 += 64) {
-        if (c0) { n = flat_counts(f, rlo, rhi, c0, lane, s4); incl = wave_scan_incl(s4, lane); }
-        const int tot = __builtin_amdgcn_readlane(incl, 63);
-        for (; i < 64; ++i) {   // this wave's tiles whose FIRST sample falls into the rows of this round
-            const int t = t0 + i * stride;
-            if (t >= tend || 32 * t - run >= tot) break;
-            const int gl = 32 * t - run;                            // offset of the tile's first sample inside this round
-            const int ls = __builtin_ctzll(__ballot(gl < incl));   // the lane whose four rows hold it
-            const int ex = __builtin_amdgcn_readlane(incl - s4, ls);
-            const int nx = __builtin_amdgcn_readlane(n.x, ls), ny = __builtin_amdgcn_readlane(n.y, ls), nz = __builtin_amdgcn_readlane(n.z, ls);
-            int r = (q0 + c0 + ls) << 2, rem = gl - ex;
-            if (rem >= nx) { rem -= nx; ++r; if (rem >= ny) { rem -= ny; ++r; if (rem >= nz) { rem -= nz; ++r; } } }
-            if (lane == i) vdesc = ((unsigned)r << 16) | ((unsigned)rem & 0xFFFFu);
-        }
-        if (t0 + i * stride >= tend) break;
-        run += tot;
-    }
-    return i;
-}
+// Tiles are looked up once per wave by the same list_fill as the dense schedule's: descriptor = first row << 16 | sample offset inside that row.
 
 // the side record of sample slot k, lane half h, of the bundle straddling window boundary b
 __device__ __forceinline__ float* flat_rec(const DevFrame& f, int b, int k, int h) {
@@ -2298,9 +2247,13 @@ __device__ __forceinline__ float* flat_rec(const DevFrame& f, int b, int k, int 
 // ---- the hand-off of a straddling bundle between its two waves (MI355X guide, "Workgroup dispatch ... inter-workgroup visibility") -----------
 // Producer side, every lane that owns a sample of a straddling bundle: its 24-float record as six WRITE-THROUGH 16-byte stores (sc1: the
 // bytes leave this XCD's L2, nothing to write back later), then the wave drains its stores (s_waitcnt vmcnt(0)) and ONE lane per boundary
-// adds 1 to the boundary's counter (agent-scope returning atomic).  The wave whose add returns 1 is the last of the two: one agent-scope
-// acquire (buffer_inv sc1), then it loads both parts' records with sc1 loads and composites the bundle.  Nobody spins, so no schedule of
-// the two waves can deadlock; the counter is returned to 0 by the last arriver (k_prepare / k_plan zero it once per frame).
+// adds 1 to the boundary's counter (agent-scope returning atomic).  The wave whose add returns 1 is the last of the two: it loads both
+// parts' records with sc1 loads (past its CU's L1) and composites the bundle.  The default build issues NO acquire there; that the loads
+// see the records rests on: a record is ONE 128-byte line that one lane writes and one wave reads, once per launch each (FLAT_REC, the
+// static_assert beside it), in a 256-byte-aligned region, so no L2 holds a line of it from before the write within the launch; and the
+// launch boundary, which invalidates what an earlier launch left.  -DGDB_FLAT_ACQUIRE adds the agent-scope acquire (buffer_inv sc1) of
+// the guide's general recipe (flat_settle).  Nobody spins, so no schedule of the two waves can deadlock; the counter is
+// returned to 0 by the last arriver (k_prepare / k_plan zero it once per frame).
 typedef float F4s __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_sc1_16(float* p, float a, float b, float c, float d) {
     const F4s v = {a, b, c, d};
@@ -2407,7 +2360,7 @@ __device__ __forceinline__ void render_list_body(const FusedArgs& a_) {
     // k_render_solo): as loop invariants those values would be live across the whole body, which has no register to spare.
     typedef const FusedArgs __attribute__((address_space(4))) KArgs;
     KArgs* const ap = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    // ---- this wave's tiles: t0, t0 + stride, ... < tend, looked up once (dense_fill / flat_fill) ---------------------------------
+    // ---- this wave's tiles: t0, t0 + stride, ... < tend, looked up once (list_fill) --------------------------------------------
     // Rows are addressed by their global index (batch item x H + row), so one launch covers the rows [row_lo, row_hi) of ALL batch
     // items (dense; the flat schedule launches per batch item), and nothing but the descriptor register and two counters lives across a tile.
     unsigned vdesc;
@@ -2416,14 +2369,9 @@ __device__ __forceinline__ void render_list_body(const FusedArgs& a_) {
         const FusedArgs& a = *(const FusedArgs*)ap;
         const int lane = threadIdx.x & 63, wv = NWG > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
         // XCD-aware order: workgroups b, b + 8, ... share an XCD (and its L2); XCD x walks the band [x chunk, (x + 1) chunk) of the tiles
-        if constexpr (FLAT) {
-            ntile = __builtin_amdgcn_readfirstlane(flat_fill(a.f, a.row_lo, a.row_hi, lane, (int)(blockIdx.x & 7), (int)(blockIdx.x >> 3) * NWG + wv,
-                                                             a.tile_stride, vdesc, t0));
-            t0 = __builtin_amdgcn_readfirstlane(t0);
-        } else {
-            ntile = __builtin_amdgcn_readfirstlane(dense_fill(a.f, a.row_lo, a.row_hi, lane, (int)(blockIdx.x & 7), (int)(blockIdx.x >> 3) * NWG + wv,
-                                                              a.tile_stride, vdesc));
-        }
+        ntile = __builtin_amdgcn_readfirstlane(list_fill<FLAT>(a.f, a.row_lo, a.row_hi, lane, (int)(blockIdx.x & 7), (int)(blockIdx.x >> 3) * NWG + wv,
+                                                               a.tile_stride, vdesc, t0));
+        if constexpr (FLAT) t0 = __builtin_amdgcn_readfirstlane(t0);
     }
     if (ntile <= 0) return;
 #ifdef GDB_DIAG
@@ -2764,30 +2712,30 @@ static hipError_t launch_solo(const FusedArgs& a, unsigned grid, size_t lds, hip
     return hipGetLastError();
 }
 
-// lds: bytes per wave (a multiple of 16).  NWG waves per workgroup: whichever of 1, 2, 4 puts the most waves on a CU (LDS comes in
-// 1280-byte granules, so several waves' areas in one allocation can fit where single ones lose a wave to the rounding); on a tie
-// the smaller workgroup, unless GDB_DENSE_PREFER_WIDE asks for the larger one (fewer workgroups for the dispatcher to launch).
-#ifndef GDB_DENSE_PREFER_WIDE
-#define GDB_DENSE_PREFER_WIDE 0
-#endif
-// Workgroups of this kernel a CU holds at once x the CUs of the device: the persistent grid.  Asked of the runtime once per
-// (kernel instantiation, device, LDS size) and kept in one atomic word per device ordinal (relaxed; two threads racing just ask twice).
+// Waves a CU holds by LDS in workgroups of n waves at `bytes` of LDS per wave: LDS is allocated per workgroup, in 1280-byte granules
+// out of 160 KiB (0: such a workgroup does not fit at all).
+static size_t lds_waves_per_cu(size_t n, size_t bytes) {
+    const size_t gran = 1280, cap = 160 * 1024;
+    return n * bytes > cap ? 0 : n * (cap / ((n * bytes + gran - 1) / gran * gran));
+}
+// Workgroups of this kernel (nwg waves, lds bytes per wave) a CU holds at once x the CUs of the device: the persistent grid.  Asked of the
+// runtime once per (kernel instantiation, device, LDS size) and kept in one atomic word per device ordinal (relaxed; two threads racing just ask twice).
 template <class K>
-static hipError_t resident_workgroups(K kernel, int threads, size_t lds, std::atomic<unsigned long long>* cache, int& per_cu, int& cus) {
+static hipError_t resident_workgroups(K kernel, int nwg, size_t lds, std::atomic<unsigned long long>* cache, int& per_cu, int& cus) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    const unsigned long long key = (unsigned long long)lds & 0x3FFFFull;
+    const unsigned long long key = (unsigned long long)(nwg * lds) & 0x3FFFFull;
     if (dev < 64) {
         const unsigned long long c = cache[dev].load(std::memory_order_relaxed);
         if ((c >> 63) && (c & 0x3FFFFull) == key) { per_cu = (int)((c >> 18) & 0xFF); cus = (int)((c >> 26) & 0xFFF); return hipSuccess; }
     }
     e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, threads, lds);
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, 64 * nwg, nwg * lds);
     if (e != hipSuccess) return e;
-    // the LDS bound as the hardware allocates it (1280-byte granules): never above it, whatever the API says
-    const int by_lds = (int)((size_t)(160 * 1024) / ((lds + 1279) / 1280 * 1280));
+    // the LDS bound as the hardware allocates it: never above it, whatever the API says
+    const int by_lds = (int)(lds_waves_per_cu(nwg, lds) / nwg);
     per_cu = per_cu < 1 ? 1 : (per_cu > by_lds ? (by_lds < 1 ? 1 : by_lds) : per_cu);
     if (per_cu > 255) per_cu = 255;
     if (cus < 1) cus = 1;
@@ -2796,136 +2744,90 @@ static hipError_t resident_workgroups(K kernel, int threads, size_t lds, std::at
     return hipSuccess;
 }
 
-template <int PREC, int WPS, int NWG, int BB = 4>
-static hipError_t launch_dense_n(FusedArgs& a, size_t lds, hipStream_t st) {
+// ---- the launcher of the two list schedules ---------------------------------------------------------------------------------------
+// The launches of one render.  One launch renders the rows [row_lo, row_hi) of the global row index (batch item x H + row).  Dense: all
+// batch items at once when the strip is the whole frame (or B = 1), one launch per batch item otherwise.  Flat: always one per batch
+// item (a window never crosses batch items).  gdb_render_info reports this number.
+static int list_launches(bool flat, int B, int H, int row_begin, int nrows) {
+    return !flat && (B == 1 || (row_begin == 0 && nrows == H)) ? 1 : B;
+}
+// Grid and tile stride of one launch: `resident` = workgroups the device holds at once, `tiles` = the launch's worst case (every bundle
+// at S_max).  The walk: the resident grid in whole octets (one octet = one workgroup per XCD), never more workgroups than the worst
+// case has tiles, never fewer than leave a wave at most 64 tiles (it keeps their descriptors in the 64 lanes of one register; 8 XCD
+// bands of ceil(tiles / 8)).  One tile per wave: the worst case.
+struct ListGrid { unsigned grid; int tile_stride; };
+static ListGrid list_grid(long long resident, long long tiles, int nwg, bool walk) {
+    resident = resident >= 8 ? resident / 8 * 8 : 8;
+    const long long worst = ((tiles + nwg - 1) / nwg + 7) / 8 * 8;
+    const long long need = 8 * (((tiles + 7) / 8 + 64LL * nwg - 1) / (64LL * nwg));
+    long long g = resident > worst ? worst : resident;
+    if (g < need) g = need;
+    if (!walk) g = worst;
+    return {(unsigned)g, (int)(g >> 3) * nwg};
+}
+template <bool FLAT, int PREC, int WPS, int NWG, bool PERSIST, int BB>
+static constexpr auto list_kernel() {
+    if constexpr (FLAT) return &k_render_flat<PREC, WPS, NWG, PERSIST>;
+    else return &k_render_dense<PREC, WPS, NWG, PERSIST, BB>;
+}
+// lds: bytes per wave (a multiple of 16).  The straddling bundles of the flat schedule are composited inside the same launch by
+// whichever of their two waves arrives last (flat_fix_boundary).
+template <bool FLAT, int PREC, int WPS, int NWG, int BB>
+static hipError_t launch_list_n(FusedArgs& a, size_t lds, hipStream_t st) {
+    // (the split-f16 flat build at three waves per SIMD has no register left for the walk's loop state: one tile per wave there)
+    constexpr bool CAN_WALK = !(FLAT && PREC == GDB_PREC_F32X && WPS == 3);
+    const auto kernel = list_kernel<FLAT, PREC, WPS, NWG, CAN_WALK, BB>();
     static std::atomic<unsigned long long> done{0}, done1{0};
     static std::atomic<unsigned long long> resident[64];
-    hipError_t e = allow_big_lds(k_render_dense<PREC, WPS, NWG, true, BB>, done);
-#ifdef GDB_DIAG   // (the one-tile-per-wave form exists in the diagnostic build only: GDB_SCHED_AUTO always walks)
-    if constexpr (BB == 4) if (e == hipSuccess) e = allow_big_lds(k_render_dense<PREC, WPS, NWG, false>, done1);
+    hipError_t e = allow_big_lds(kernel, done);
+#ifdef GDB_DIAG   // (beside a build that walks, the one-tile-per-wave form exists in the diagnostic build only; centre-ray form: always the walk)
+    const auto one_tile = list_kernel<FLAT, PREC, WPS, NWG, false, 4>();
+    if constexpr (BB == 4) if (e == hipSuccess) e = allow_big_lds(one_tile, done1);
 #endif
     (void)done1;
     if (e != hipSuccess) return e;
     int per_cu = 1, cus = 1;
-    e = resident_workgroups(k_render_dense<PREC, WPS, NWG, true, BB>, 64 * NWG, NWG * lds, resident, per_cu, cus);
+    e = resident_workgroups(kernel, NWG, lds, resident, per_cu, cus);
     if (e != hipSuccess) return e;
-#ifdef GDB_DIAG  // diagnostic build: over- / under-subscribe the persistent grid (workgroups per CU) from the environment
+    // Tile walk or one tile per wave: both forms are exact, the choice is speed only - always the walk (profiles/r04/ab_walk_vs_one_tile.txt).
+    bool walk = CAN_WALK;
+#ifdef GDB_DIAG  // diagnostic build: over- / under-subscribe the persistent grid (workgroups per CU), or take the one-tile form, from the environment
     static const int env_wgs = getenv("GDB_DENSE_WGS_PER_CU") ? atoi(getenv("GDB_DENSE_WGS_PER_CU")) : 0;
+    static const int env_persist = getenv("GDB_DENSE_PERSIST") ? atoi(getenv("GDB_DENSE_PERSIST")) : -1;
     if (env_wgs > 0) per_cu = env_wgs;
+    if (env_persist >= 0 && BB == 4) walk = CAN_WALK && env_persist != 0;
 #endif
-    // The resident grid, shared between the batch items (grid y), never more workgroups than the worst case has tiles
-    // (a.ntiles: every bundle at S_max), a multiple of 8 (one octet = one workgroup per XCD).
-    long long grid = (long long)per_cu * cus;
-    grid = grid >= 8 ? grid / 8 * 8 : 8;
-    // One launch renders the rows [row_lo, row_hi) of the global row index (batch item x H + row): all batch items at once when
-    // the strip is the whole frame (or B = 1), one launch per batch item otherwise.
-    const bool whole = a.f.B == 1 || (a.row_begin == 0 && a.nrows == a.f.H);
-    const int nl = whole ? 1 : a.f.B;
+    const int nl = list_launches(FLAT, a.f.B, a.f.H, a.row_begin, a.nrows);
     for (int l = 0; l < nl; ++l) {
-        a.row_lo = (whole ? 0 : l * a.f.H) + a.row_begin;
-        a.row_hi = whole ? (a.f.B - 1) * a.f.H + a.row_begin + a.nrows : a.row_lo + a.nrows;
-        // never more workgroups than the worst case has tiles (every bundle at S_max)
-        const long long tiles = (long long)(a.row_hi - a.row_lo) * a.f.planMW;
-        const long long worst = ((tiles + NWG - 1) / NWG + 7) / 8 * 8;
-        long long g = grid > worst ? worst : grid;
-        // a wave keeps its tiles' descriptors in the 64 lanes of one register: at most 64 tiles per wave (8 XCD bands of ceil(tiles / 8))
-        const long long need = 8 * (((tiles + 7) / 8 + 64LL * NWG - 1) / (64LL * NWG));
-        if (g < need) g = need;
-        // Tile walk or one tile per wave: both forms are exact, the choice is speed only.  Measured on one MI355X, same process order
-        // (profiles/r04/ab_walk_vs_one_tile.txt; kernel us, walk / one tile per wave): c2 fp32 99.8 / 102.9, f16 50.8 / 52.4; c4 (S_max
-        // 6) fp32 202.9 / 206.0, f16 105.2 / 112.2, split-f16 140.0 / 146.3; but c3 fp32 181.6 / 175.7, f16 94.6 / 92.3; c3' fp32
-        // 216.6 / 209.8.  The walk saves the dispatcher's gap between two tiles of a wave slot; the dispatcher's dynamic order balances
-        // the long S_max 3 frames better than a static stride.  Rule fitted to those rows: the walk while the worst case is at most
-        // three tiles per resident wave, or when S_max > 4.
-        // (Round 4, with the walk's wave priorities in place - profiles/r04/ab_walk_vs_one_tile.txt, second table: the walk now wins on the
-        // long S_max 3 frames too: c3 fp32 174.9 / 176.2, c3' 210.4 / 211.0, c3 f16 87.8 / 93.8, split-f16 115.7 / 120.5 - always the walk.)
-        bool persist = true;
+        a.row_lo = l * a.f.H + a.row_begin;
+        a.row_hi = (nl == 1 ? (a.f.B - 1) * a.f.H : l * a.f.H) + a.row_begin + a.nrows;
+        const long long rows = a.row_hi - a.row_lo;
+        const long long tiles = FLAT ? (rows * a.f.W * a.f.S_max + 31) / 32 + 1 : rows * a.f.planMW;   // worst case: every bundle at S_max
+        if constexpr (FLAT) a.flat_base = l * (int)(((long long)a.f.H * a.f.W * a.f.S_max + 31) / 32 + 2);   // window boundaries of a batch item, as WsLayout::flatMaxTiles
+        const ListGrid g = list_grid((long long)per_cu * cus, tiles, NWG, walk);
+        a.tile_stride = g.tile_stride;
 #ifdef GDB_DIAG
-        static const int env_persist = getenv("GDB_DENSE_PERSIST") ? atoi(getenv("GDB_DENSE_PERSIST")) : -1;
-        if (env_persist >= 0 && BB == 4) persist = env_persist != 0;
-#endif
-        if (!persist) g = worst;
-        a.tile_stride = (int)(g >> 3) * NWG;
-#ifdef GDB_DIAG
-        if (!persist && BB == 4) hipLaunchKernelGGL((k_render_dense<PREC, WPS, NWG, false>), dim3((unsigned)g), dim3(64 * NWG), NWG * lds, st, a);
+        if (walk != CAN_WALK) hipLaunchKernelGGL(one_tile, dim3(g.grid), dim3(64 * NWG), NWG * lds, st, a);
         else
 #endif
-        hipLaunchKernelGGL((k_render_dense<PREC, WPS, NWG, true, BB>), dim3((unsigned)g), dim3(64 * NWG), NWG * lds, st, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipGetLastError();
-}
-template <int PREC, int WPS>
-static hipError_t launch_dense(FusedArgs& a, size_t lds, hipStream_t st) {
-    const size_t gran = 1280, cap = 160 * 1024;
-    auto waves = [&](size_t n) { return n * lds > cap ? (size_t)0 : n * (cap / ((n * lds + gran - 1) / gran * gran)); };
-    const size_t w1 = waves(1), w2 = waves(2), w4 = waves(4);
-    a.wave_floats = (int)(lds / sizeof(float));
-    const bool wide = GDB_DENSE_PREFER_WIDE != 0;
-    if ((w4 > w2 && w4 > w1) || (wide && w4 >= w2 && w4 >= w1 && w4 > 0)) return launch_dense_n<PREC, WPS, 4>(a, lds, st);
-    if (w2 > w1 || (wide && w2 >= w1 && w2 > 0)) return launch_dense_n<PREC, WPS, 2>(a, lds, st);
-    return launch_dense_n<PREC, WPS, 1>(a, lds, st);
-}
-
-// Flat schedule: one launch of k_render_flat per batch item (a window never crosses batch items); the bundles that straddle a window
-// boundary are composited inside the same launch by whichever of their two waves arrives last (flat_fix_boundary).  Grid as launch_dense_n.
-template <int PREC, int WPS, int NWG>
-static hipError_t launch_flat_n(FusedArgs& a, size_t lds, int max_tiles_per_item, hipStream_t st) {
-    // (the split-f16 build at three waves per SIMD has no register left for the walk's loop state: one tile per wave there)
-    constexpr bool CAN_WALK = !(PREC == GDB_PREC_F32X && WPS == 3);
-    static std::atomic<unsigned long long> done{0}, done1{0};
-    static std::atomic<unsigned long long> resident[64];
-    hipError_t e = allow_big_lds(k_render_flat<PREC, WPS, NWG, CAN_WALK>, done);
-#ifdef GDB_DIAG
-    if (e == hipSuccess) e = allow_big_lds(k_render_flat<PREC, WPS, NWG, false>, done1);
-#endif
-    (void)done1;
-    if (e != hipSuccess) return e;
-    int per_cu = 1, cus = 1;
-    e = resident_workgroups(k_render_flat<PREC, WPS, NWG, CAN_WALK>, 64 * NWG, NWG * lds, resident, per_cu, cus);
-    if (e != hipSuccess) return e;
-#ifdef GDB_DIAG
-    static const int env_wgs = getenv("GDB_DENSE_WGS_PER_CU") ? atoi(getenv("GDB_DENSE_WGS_PER_CU")) : 0;
-    if (env_wgs > 0) per_cu = env_wgs;
-#endif
-    long long grid = (long long)per_cu * cus;
-    grid = grid >= 8 ? grid / 8 * 8 : 8;
-    for (int bi = 0; bi < a.f.B; ++bi) {
-        a.row_lo = bi * a.f.H + a.row_begin;
-        a.row_hi = a.row_lo + a.nrows;
-        a.flat_base = bi * (max_tiles_per_item + 1);
-        const long long tiles = ((long long)a.nrows * a.f.W * a.f.S_max + 31) / 32 + 1;   // worst case: every bundle at S_max
-        const long long worst = ((tiles + NWG - 1) / NWG + 7) / 8 * 8;
-        long long g = grid > worst ? worst : grid;
-        const long long need = 8 * (((tiles + 7) / 8 + 64LL * NWG - 1) / (64LL * NWG));   // at most 64 tiles per wave (one descriptor per lane)
-        if (g < need) g = need;
-        bool persist = CAN_WALK;   // (always the walk where the build can, as launch_dense_n)
-#ifdef GDB_DIAG
-        static const int env_persist = getenv("GDB_DENSE_PERSIST") ? atoi(getenv("GDB_DENSE_PERSIST")) : -1;
-        if (env_persist >= 0) persist = CAN_WALK && env_persist != 0;
-#endif
-        if (!persist) g = worst;
-        a.tile_stride = (int)(g >> 3) * NWG;
-#ifdef GDB_DIAG
-        if (!persist && CAN_WALK) hipLaunchKernelGGL((k_render_flat<PREC, WPS, NWG, false>), dim3((unsigned)g), dim3(64 * NWG), NWG * lds, st, a);
-        else
-#endif
-        hipLaunchKernelGGL((k_render_flat<PREC, WPS, NWG, CAN_WALK>), dim3((unsigned)g), dim3(64 * NWG), NWG * lds, st, a);
+        hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(64 * NWG), NWG * lds, st, a);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
-template <int PREC, int WPS>
-static hipError_t launch_flat(FusedArgs& a, size_t lds, int max_tiles_per_item, hipStream_t st) {
-    const size_t gran = 1280, cap = 160 * 1024;
-    auto waves = [&](size_t n) { return n * lds > cap ? (size_t)0 : n * (cap / ((n * lds + gran - 1) / gran * gran)); };
-    const size_t w1 = waves(1), w2 = waves(2), w4 = waves(4);
+// NWG waves per workgroup: whichever of 1, 2, 4 puts the most waves on a CU (several waves' areas in one LDS allocation can fit where
+// single ones lose a wave to the granule rounding); on a tie the smaller workgroup.  Centre-ray form: two.
+template <bool FLAT, int PREC, int WPS, int BB>
+static hipError_t launch_list(FusedArgs& a, size_t lds, hipStream_t st) {
     a.wave_floats = (int)(lds / sizeof(float));
-    if (w4 > w2 && w4 > w1) return launch_flat_n<PREC, WPS, 4>(a, lds, max_tiles_per_item, st);
-    if (w2 > w1) return launch_flat_n<PREC, WPS, 2>(a, lds, max_tiles_per_item, st);
-    return launch_flat_n<PREC, WPS, 1>(a, lds, max_tiles_per_item, st);
+    if constexpr (BB == 1) return launch_list_n<FLAT, PREC, WPS, 2, BB>(a, lds, st);
+    else {
+        const size_t w1 = lds_waves_per_cu(1, lds), w2 = lds_waves_per_cu(2, lds), w4 = lds_waves_per_cu(4, lds);
+        if (w4 > w2 && w4 > w1) return launch_list_n<FLAT, PREC, WPS, 4, BB>(a, lds, st);
+        if (w2 > w1) return launch_list_n<FLAT, PREC, WPS, 2, BB>(a, lds, st);
+        return launch_list_n<FLAT, PREC, WPS, 1, BB>(a, lds, st);
+    }
 }
 
 template <bool LOOP, int WAVES, int PREC>
@@ -3009,55 +2911,6 @@ __global__ void __launch_bounds__(256) k_bundle_colours(ColArgs a) {
     }
 }
 
-static size_t solo_lds_bytes(int prec, int V);
-static bool dense_fits(const GdbFrame& fr);
-// The two launches of a bundle_size 1 / 4 render: the list kernel on the bundles' centre rays (dense schedule, two waves per workgroup,
-// the walk), then the colours.  f32x operand pairs are not built in this form: that precision runs the fp32 kernel (which is the more
-// exact of the two).
-template <int PREC, int WPS>
-static int render_center_launch(FusedArgs& a, const GdbConfig* cfg, const GdbFrame* fr, const WsLayout& L, const void* ws, bool plan_ready,
-                                float* bf, float* depth, float* opac, int ldo, hipStream_t st) {
-    if (!dense_fits(*fr)) return gdb_fail(GDB_E_SHAPE, "the dense schedule lists bundles and rows in 16 bits: W = %d, B x H = %lld (both must be < 65536)", fr->W, (long long)fr->B * fr->H);
-    if (!plan_ready) {
-        int rc = gdb_build_dense_plan(cfg, fr, const_cast<void*>(ws), st);
-        if (rc) return rc;
-    }
-    a.alias = 0;
-    a.bf = (float*)((char*)const_cast<void*>(ws) + L.colTmpOff); a.depth = nullptr; a.opac = nullptr; a.ldo = NOUT + 2;
-    a.wv = (float*)((char*)const_cast<void*>(ws) + L.colWvOff);
-    a.ntiles = a.nrows * a.f.planMW;
-    const size_t lds = (solo_lds_bytes(PREC, fr->V) + 15) / 16 * 16;
-    a.wave_floats = (int)(lds / sizeof(float));
-    if (2 * lds > (size_t)160 * 1024) return gdb_fail(GDB_E_SHAPE, "V=%d needs %zu B of LDS per wave (two waves per workgroup exceed 160 KiB)", fr->V, lds);
-    hipError_t e = launch_dense_n<PREC, WPS, 2, 1>(a, lds, st);
-    if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "launch k_render_dense (centre rays): %s", hipGetErrorString(e));
-    ColArgs c;
-    c.f = a.f; c.wv = a.wv; c.tmp = a.bf; c.bf = bf; c.depth = depth; c.opac = opac; c.ldo = ldo; c.row_begin = a.row_begin; c.nrows = a.nrows;
-    const int BB = cfg->bundle_size * cfg->bundle_size;
-    const long long threads = (long long)fr->B * a.nrows * fr->W * BB;
-    const unsigned grid = (unsigned)((threads + 255) / 256);
-    if (BB == 16) hipLaunchKernelGGL(k_bundle_colours<16>, dim3(grid), dim3(256), 0, st, c);
-    else hipLaunchKernelGGL(k_bundle_colours<1>, dim3(grid), dim3(256), 0, st, c);
-    e = hipGetLastError();
-    if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "launch k_bundle_colours: %s", hipGetErrorString(e));
-    return GDB_OK;
-}
-
-// one-wave workgroups a CU holds by LDS (allocated in 1280-byte granules out of 160 KiB)
-static size_t waves_by_lds(size_t lds) { return (size_t)(160 * 1024) / ((lds + 1279) / 1280 * 1280); }
-
-// Compute units of the current device, asked once per device ordinal (relaxed; two threads racing just ask twice).
-static int device_cus() {
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (dev >= 0 && dev < 64) { const int c = cache[dev].load(std::memory_order_relaxed); if (c > 0) return c; }
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    if (dev >= 0 && dev < 64) cache[dev].store(cus, std::memory_order_relaxed);
-    return cus;
-}
-
 // LDS per wave of the one-wave schedules (segment wave, dense, flat): the views' staging rows, or the output record where that is larger
 static size_t solo_lds_bytes(int prec, int V) {
     const size_t sv = prec == GDB_PREC_F16 ? stage_v<GDB_PREC_F16>() : stage_v<GDB_PREC_F32>();
@@ -3073,6 +2926,77 @@ static bool flat_fits(const GdbConfig& cfg, const GdbFrame& fr, const WsLayout& 
     return dense_fits(fr) && (long long)fr.W * S < 65536 && (long long)fr.H * fr.W < (1 << 24) && S <= 16 &&
            (unsigned long long)fr.B * fr.H * (unsigned long long)L.smapStride * 4ull < (1ull << 32);
 }
+// What both launch paths of the list schedules check first: the schedule's 16-bit fields hold the frame, and the plan + sample list
+// exist - built here, into the plan region of the caller's workspace (a launch of its own on the same stream), unless the caller
+// vouches that gdb_prepare built them from the depth prior as it stands (GDB_SCHED_PLAN_READY).
+static int ensure_list_plan(int run, const GdbConfig* cfg, const GdbFrame* fr, const WsLayout& L, const void* ws, bool plan_ready, hipStream_t st) {
+    if (run == GDB_SCHED_FLAT && !flat_fits(*cfg, *fr, L))
+        return gdb_fail(GDB_E_SHAPE, "the flat schedule needs W x S_max < 65536, B x H < 65536, H x W < 2^24 (W = %d, H = %d, B = %d, S_max = %d)", fr->W, fr->H, fr->B, cfg->max_num_samples);
+    if (run == GDB_SCHED_DENSE && !dense_fits(*fr))
+        return gdb_fail(GDB_E_SHAPE, "the dense schedule lists bundles and rows in 16 bits: W = %d, B x H = %lld (both must be < 65536)", fr->W, (long long)fr->B * fr->H);
+    return plan_ready ? GDB_OK : gdb_build_dense_plan(cfg, fr, const_cast<void*>(ws), st);
+}
+// Waves per SIMD of the list kernels' build (__launch_bounds__) for a precision, schedule and form; by_lds = waves per CU that LDS admits.
+//  * fp32: the two-wave bound.
+//  * split-f16: the three-wave build (168 registers) wherever LDS admits more than the 8 waves per CU of the two-wave build.
+//  * f16 (round 5): its list kernels need 142 registers whatever they are allowed (so there is no two-wave build of them), and fit into
+//    the 128 of FOUR waves per SIMD without a spill: that build wherever LDS admits all 16 waves per CU (V <= 4; c2 f16 42.2 -> 39.8 us,
+//    c3 71.3 -> 67.0, c4 81.9 -> 78.2.  At V = 5 LDS admits 14, and the 4-wave build with 14 is SLOWER than the 3-wave one with 12: c5
+//    forced onto this schedule 744 -> 777 us, profiles/r05/ab_f16_four_waves.txt).  Stays at three where four would spill: the flat
+//    body (7 registers) and, with the colour weights, the centre-ray body (4).
+static constexpr int list_waves_per_simd(int prec, bool flat, bool centre, size_t by_lds) {
+    if (prec == GDB_PREC_F16) return !flat && !centre && by_lds >= 16 ? 4 : 3;
+    if (prec == GDB_PREC_F32X) return by_lds > 8 ? 3 : 2;
+    return 2;
+}
+// ... and the one dispatch to that build.  The builds that exist are the ones the rule names where LDS admits nothing and everything.
+template <bool FLAT, int PREC, int BB>
+static hipError_t launch_list_wps(FusedArgs& a, size_t lds, size_t by_lds, hipStream_t st) {
+    constexpr int LO = list_waves_per_simd(PREC, FLAT, BB == 1, 0), HI = list_waves_per_simd(PREC, FLAT, BB == 1, ~(size_t)0);
+    if constexpr (HI != LO) if (list_waves_per_simd(PREC, FLAT, BB == 1, by_lds) == HI) return launch_list<FLAT, PREC, HI, BB>(a, lds, st);
+    return launch_list<FLAT, PREC, LO, BB>(a, lds, st);
+}
+
+// The two launches of a bundle_size 1 / 4 render: the list kernel on the bundles' centre rays (dense schedule, two waves per workgroup,
+// the walk), then the colours.  f32x operand pairs are not built in this form: that precision runs the fp32 kernel (which is the more
+// exact of the two).
+template <int PREC>
+static int render_center_launch(FusedArgs& a, const GdbConfig* cfg, const GdbFrame* fr, const WsLayout& L, const void* ws, bool plan_ready,
+                                float* bf, float* depth, float* opac, int ldo, hipStream_t st) {
+    int rc = ensure_list_plan(GDB_SCHED_DENSE, cfg, fr, L, ws, plan_ready, st);
+    if (rc) return rc;
+    a.alias = 0;
+    a.bf = (float*)((char*)const_cast<void*>(ws) + L.colTmpOff); a.depth = nullptr; a.opac = nullptr; a.ldo = NOUT + 2;
+    a.wv = (float*)((char*)const_cast<void*>(ws) + L.colWvOff);
+    a.ntiles = a.nrows * a.f.planMW;
+    const size_t lds = (solo_lds_bytes(PREC, fr->V) + 15) / 16 * 16;
+    if (!lds_waves_per_cu(2, lds)) return gdb_fail(GDB_E_SHAPE, "V=%d needs %zu B of LDS per wave (two waves per workgroup exceed 160 KiB)", fr->V, lds);
+    hipError_t e = launch_list_wps<false, PREC, 1>(a, lds, 0, st);
+    if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "launch k_render_dense (centre rays): %s", hipGetErrorString(e));
+    ColArgs c;
+    c.f = a.f; c.wv = a.wv; c.tmp = a.bf; c.bf = bf; c.depth = depth; c.opac = opac; c.ldo = ldo; c.row_begin = a.row_begin; c.nrows = a.nrows;
+    const int BB = cfg->bundle_size * cfg->bundle_size;
+    const long long threads = (long long)fr->B * a.nrows * fr->W * BB;
+    const unsigned grid = (unsigned)((threads + 255) / 256);
+    if (BB == 16) hipLaunchKernelGGL(k_bundle_colours<16>, dim3(grid), dim3(256), 0, st, c);
+    else hipLaunchKernelGGL(k_bundle_colours<1>, dim3(grid), dim3(256), 0, st, c);
+    e = hipGetLastError();
+    if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "launch k_bundle_colours: %s", hipGetErrorString(e));
+    return GDB_OK;
+}
+
+// Compute units of the current device, asked once per device ordinal (relaxed; two threads racing just ask twice).
+static int device_cus() {
+    static std::atomic<int> cache[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    if (dev >= 0 && dev < 64) { const int c = cache[dev].load(std::memory_order_relaxed); if (c > 0) return c; }
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+    if (dev >= 0 && dev < 64) cache[dev].store(cus, std::memory_order_relaxed);
+    return cus;
+}
+
 // The ONE place that decides what a fused render call runs: `sched` as the caller passed it (GDB_SCHED_AUTO .. GDB_SCHED_FLAT) -> the
 // schedule launched (GDB_SCHED_SLOT_WAVES .. GDB_SCHED_FLAT).  gdb_render_info() exports it (bench.py, HotPathEngine: no second copy of
 // the rule in Python).  Measured choices (MI355X; profiles/r01/schedules.txt, r03/schedules.txt, r04/ab_*.txt, r05/ab_*.txt):
@@ -3116,45 +3040,23 @@ static int render_launch(FusedArgs& a, const GdbConfig* cfg, const GdbFrame* fr,
 #endif
     const int run = resolve_schedule(*cfg, *fr, L, PREC, a.nrows, sched);
     if (run == GDB_SCHED_FLAT || run == GDB_SCHED_DENSE) {
-        if (run == GDB_SCHED_FLAT && !flat_fits(*cfg, *fr, L))
-            return gdb_fail(GDB_E_SHAPE, "the flat schedule needs W x S_max < 65536, B x H < 65536, H x W < 2^24 (W = %d, H = %d, B = %d, S_max = %d)", fr->W, fr->H, fr->B, S);
-        if (run == GDB_SCHED_DENSE && !dense_fits(*fr))
-            return gdb_fail(GDB_E_SHAPE, "the dense schedule lists bundles and rows in 16 bits: W = %d, B x H = %lld (both must be < 65536)", fr->W, (long long)fr->B * fr->H);
-        // The plan + sample list are built here, into the plan region of the caller's workspace (a launch of its own on the same
-        // stream), unless the caller vouches that gdb_prepare built them from the depth prior as it stands (GDB_SCHED_PLAN_READY).
-        if (!plan_ready) {
-            int rc = gdb_build_dense_plan(cfg, fr, const_cast<void*>(ws), st);
-            if (rc) return rc;
-        }
+        int rc = ensure_list_plan(run, cfg, fr, L, ws, plan_ready, st);
+        if (rc) return rc;
         a.alias = 0;
-        // the 3-waves-per-SIMD build (168 registers) wherever LDS admits more than the 8 waves per CU of the 2-wave build.
-        // GDB_PREC_F16 (round 5): its list kernels need 142 registers whatever they are allowed (so there is no 2-wave build of them), and
-        // fit into the 128 of FOUR waves per SIMD without a spill: that build wherever LDS admits all 16 waves per CU (V <= 4; c2 f16 42.2 ->
-        // 39.8 us, c3 71.3 -> 67.0, c4 81.9 -> 78.2.  At V = 5 LDS admits 14, and the 4-wave build with 14 is SLOWER than the 3-wave one with
-        // 12: c5 forced onto this schedule 744 -> 777 us, profiles/r05/ab_f16_four_waves.txt).
-        const size_t by_lds = waves_by_lds(solo_lds + pad) > 2 * waves_by_lds(2 * (solo_lds + pad)) ? waves_by_lds(solo_lds + pad) : 2 * waves_by_lds(2 * (solo_lds + pad));
-        bool three = false;
-        if constexpr (PREC == GDB_PREC_F32X) three = by_lds > 8;
-        const bool four = PREC == GDB_PREC_F16 && by_lds >= 16;
+        const size_t w1 = lds_waves_per_cu(1, solo_lds + pad), w2 = lds_waves_per_cu(2, solo_lds + pad), by_lds = w1 > w2 ? w1 : w2;
         const size_t lds = (solo_lds + pad + 15) / 16 * 16;
         if (run == GDB_SCHED_FLAT) {
-            const int max_tiles = (int)(((long long)fr->H * fr->W * S + 31) / 32 + 1);
-            if constexpr (PREC == GDB_PREC_F16) e = launch_flat<PREC, 3>(a, lds, max_tiles, st);   // (the flat body spills 7 registers at four waves per SIMD)
-            else if constexpr (PREC == GDB_PREC_F32X) e = three ? launch_flat<PREC, 3>(a, lds, max_tiles, st) : launch_flat<PREC, 2>(a, lds, max_tiles, st);
-            else e = launch_flat<PREC, 2>(a, lds, max_tiles, st);
+            e = launch_list_wps<true, PREC, 4>(a, lds, by_lds, st);
             if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "launch k_render_flat: %s", hipGetErrorString(e));
             return GDB_OK;
         }
         a.ntiles = a.nrows * a.f.planMW;  // per batch item, worst case (every bundle at S_max)
-        grid = (unsigned)((a.ntiles + 7) / 8 * 8);
-        if constexpr (PREC == GDB_PREC_F16) e = four ? launch_dense<PREC, 4>(a, lds, st) : launch_dense<PREC, 3>(a, lds, st);
-        else if constexpr (PREC == GDB_PREC_F32X) e = three ? launch_dense<PREC, 3>(a, lds, st) : launch_dense<PREC, 2>(a, lds, st);
-        else e = launch_dense<PREC, 2>(a, lds, st);
+        e = launch_list_wps<false, PREC, 4>(a, lds, by_lds, st);
     } else if (run == GDB_SCHED_SEGMENT_WAVE) {  // one wave per segment, all slots in turn
         a.alias = 0;
         // three waves per SIMD only where LDS admits them (12 one-wave workgroups per CU) and the precision's register budget does
         bool three = false;
-        if constexpr (PREC == GDB_PREC_F16) three = waves_by_lds(solo_lds + pad) > 8;
+        if constexpr (PREC == GDB_PREC_F16) three = lds_waves_per_cu(1, solo_lds + pad) > 8;
         if constexpr (PREC == GDB_PREC_F16) { if (three) e = launch_solo<GDB_PREC_F16, 3>(a, grid, solo_lds + pad, st); }
         if (!three) e = launch_solo<PREC, 2>(a, grid, solo_lds + pad, st);
     } else if (rec_fits && S <= 8 && (size_t)S * per_wave <= lds_max) {  // one wave per slot
@@ -3186,7 +3088,8 @@ extern "C" int gdb_render_info(const GdbConfig* cfg, const GdbFrame* fr, int32_t
     out[0] = fr->V >= 2 ? 1 : 0;   // (bundle_size 1 / 4 since round 6: the dense list kernel on the centre rays + k_bundle_colours)
     out[1] = !out[0] ? 0 : cfg->bundle_size != 2 ? GDB_SCHED_DENSE : resolve_schedule(*cfg, *fr, L, precision, row_end - row_begin, GDB_SCHED_AUTO);
     out[2] = (cfg->is_adaptive || gdb_fixed_counts_dense(*cfg, fr->V)) ? 1 : 0;   // gdb_prepare builds the plan when the frame carries d_depth_range (gdb_ops.hip prepare_common)
-    out[3] = out[0] ? ((out[1] == GDB_SCHED_FLAT || (out[1] == GDB_SCHED_DENSE && fr->B > 1 && !(row_begin == 0 && row_end == fr->H))) ? fr->B : 1) + (cfg->bundle_size != 2 ? 1 : 0) : 0;
+    const bool list = out[1] == GDB_SCHED_FLAT || out[1] == GDB_SCHED_DENSE;
+    out[3] = out[0] ? (list ? list_launches(out[1] == GDB_SCHED_FLAT, fr->B, fr->H, row_begin, row_end - row_begin) : 1) + (cfg->bundle_size != 2 ? 1 : 0) : 0;
     return GDB_OK;
 }
 
@@ -3241,9 +3144,8 @@ static int render_entry(const GdbConfig* cfg, const GdbFrame* fr, const void* ws
     if (b != 2) {
         // bundle_size 1 / 4: the dense list kernel on the bundles' centre rays, then the sub-ray colours (two launches; `schedule` beyond
         // its flags is ignored: this form has the one schedule).  f32x runs the fp32 kernel.
-        // (f16: the three-waves-per-SIMD build - with the colour weights the centre-ray body spills four registers at four)
-        if (precision == GDB_PREC_F16) return render_center_launch<GDB_PREC_F16, 3>(a, cfg, fr, L, ws, plan_ready, bf, depth, opac, ldo, st);
-        return render_center_launch<GDB_PREC_F32, 2>(a, cfg, fr, L, ws, plan_ready, bf, depth, opac, ldo, st);
+        if (precision == GDB_PREC_F16) return render_center_launch<GDB_PREC_F16>(a, cfg, fr, L, ws, plan_ready, bf, depth, opac, ldo, st);
+        return render_center_launch<GDB_PREC_F32>(a, cfg, fr, L, ws, plan_ready, bf, depth, opac, ldo, st);
     }
     if (precision == GDB_PREC_F32) return render_launch<GDB_PREC_F32>(a, cfg, fr, L, ws, schedule, plan_ready, st);
     if (precision == GDB_PREC_F32X) return render_launch<GDB_PREC_F32X>(a, cfg, fr, L, ws, schedule, plan_ready, st);

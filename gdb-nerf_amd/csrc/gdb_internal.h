@@ -117,6 +117,9 @@ struct WsLayout {
 #ifndef FLAT_REC
 #define FLAT_REC 32
 #endif
+#ifndef GDB_FLAT_ACQUIRE   // (with the acquire the hand-off does not rest on the line rule)
+static_assert(FLAT_REC * sizeof(float) % 128 == 0, "without GDB_FLAT_ACQUIRE the flat hand-off rests on whole 128-byte lines per side record");
+#endif
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // Fixed sample counts (is_adaptive = 0) for which GDB_SCHED_AUTO takes the DENSE schedule at fp32 / split-f16 (the sample list is then

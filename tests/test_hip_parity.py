@@ -13,6 +13,8 @@ Tolerances (float32, absolute unless stated):
     frames (fp32 coordinate noise on white-noise features: FUSED_TOL_F32) and 2e-5 on the smooth-feature c2 frame, where that noise
     is out of the way and the bound sees the arithmetic; PSNR delta <= 0.05 dB.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -329,23 +331,37 @@ def test_fused_vs_golden(tag, mode):
     assert max_abs(npy(opac), fx["opacity"]) <= 1e-5
 
 
+def tall_frame():
+    """528x16 px, B = 2: 264 bundle rows of 8 bundles per item.  A strip of more than 256 rows makes the list schedules' tile lookup take
+    its second round of per-row counts and the separate total pass; every flat window spans at least two rows."""
+    return synthetic.make_frame(528, 16, V=3, B=2, seed=4)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_case(Ho, Wo, V, B, S, adaptive, inv, scene):
+    """One frame, weights and oracle render per row of test_fused_vs_oracle, shared by the twelve modes (read-only)."""
+    frame = tall_frame() if scene is None else synthetic.make_frame(Ho, Wo, V=V, B=B, scene=scene, seed=21, src_focal_scale=(1.0, 1.9, 3.3))
+    w = synthetic.make_nerf_weights(seed=5)
+    with np.errstate(all="ignore"):
+        obf, od, oo = oracle.hot_path(frame, w, max_num_samples=S, is_adaptive=adaptive, inv_depth=inv)
+    return frame, w, obf, od, oo
+
+
 @pytest.mark.parametrize("Ho,Wo,V,B,S,adaptive,inv,scene", [
     (64, 80, 3, 1, 3, True, False, "dtu"),     # c1
     (64, 80, 3, 1, 6, False, False, "dtu"),    # fixed count, waves loop over slots
     (96, 72, 4, 2, 6, True, True, "nerf"),     # ragged row (W=36), batch 2, disparity sampling
     (48, 80, 2, 1, 3, True, False, "llff"),
     (32, 64, 5, 1, 8, True, False, "dtu"),     # 5 views, 8 slots
+    (528, 16, 3, 2, 3, True, False, None),     # tall_frame(): 264 rows of 8 bundles per item - the tile lookup's second round of counts
 ])
 def test_fused_vs_oracle(Ho, Wo, V, B, S, adaptive, inv, scene, mode):
-    frame = synthetic.make_frame(Ho, Wo, V=V, B=B, scene=scene, seed=21, src_focal_scale=(1.0, 1.9, 3.3))
-    w = synthetic.make_nerf_weights(seed=5)
-    with np.errstate(all="ignore"):
-        obf, od, oo = oracle.hot_path(frame, w, max_num_samples=S, is_adaptive=adaptive, inv_depth=inv)
+    frame, w, obf, od, oo = _oracle_case(Ho, Wo, V, B, S, adaptive, inv, scene)
     eng = engine_for(frame, w, mode, max_num_samples=S, is_adaptive=adaptive, inv_depth=inv)
     bf, depth, opac = eng.render()
     e = max_abs(npy(bf), obf)
     print(f"fused vs oracle {Ho}x{Wo} V{V} S{S}: max abs err {e:.3e}, rms {np.sqrt(np.mean((npy(bf)-obf)**2)):.3e}")
-    assert e <= fused_tol(mode)
+    assert e <= fused_tol(mode, "small" if max(Ho, Wo) <= 128 else "c2")
     assert max_abs(npy(depth), od) <= 2e-3 * float(np.abs(od).max())
     assert max_abs(npy(opac), oo) <= 1e-5
     assert _psnr_delta(npy(bf), obf, Ho // 2, Wo // 2) <= 0.05
@@ -636,18 +652,20 @@ def test_hot_path_step_replays_from_a_hip_graph(prec, sched):
 
 def test_fused_row_strips_tile_the_frame(mode):
     """Row-strip launches (the multi-GPU shard unit) reproduce the full-frame launch bit for bit."""
-    frame = synthetic.make_frame(64, 80, V=3, B=2, seed=4)
     w = synthetic.make_nerf_weights(seed=1)
-    eng = engine_for(frame, w, mode)
-    full = [t.clone() for t in eng.render()]
-    nb = eng.n_bundles
-    out = (torch.zeros((nb, eng.Q), device="cuda"), torch.zeros(nb, device="cuda"), torch.zeros(nb, device="cuda"))
-    for r0, r1 in ((0, 5), (5, 6), (6, 32)):
-        eng.render(r0, r1, None, out)
-    for a, b in zip(full, out):
-        assert torch.equal(a, b)
-    with pytest.raises(ValueError, match="row strip"):
-        eng.render(3, 40)
+    # (the tall frame's middle strip starts off a multiple of four and spans more than 256 rows)
+    for frame, strips in ((synthetic.make_frame(64, 80, V=3, B=2, seed=4), ((0, 5), (5, 6), (6, 32))),
+                          (tall_frame(), ((0, 3), (3, 259), (259, 264)))):
+        eng = engine_for(frame, w, mode)
+        full = [t.clone() for t in eng.render()]
+        nb = eng.n_bundles
+        out = (torch.zeros((nb, eng.Q), device="cuda"), torch.zeros(nb, device="cuda"), torch.zeros(nb, device="cuda"))
+        for r0, r1 in strips:
+            eng.render(r0, r1, None, out)
+        for a, b in zip(full, out):
+            assert torch.equal(a, b)
+        with pytest.raises(ValueError, match="row strip"):
+            eng.render(3, strips[-1][1] + 8)
 
 
 def test_single_view_is_rejected_by_fused_and_nan_in_mirror():
