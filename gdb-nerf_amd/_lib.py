@@ -125,6 +125,11 @@ _SIGNATURES = {
     "gdb_lpips_workspace_bytes": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_size_t)]),
     "gdb_lpips_layout": (C.c_int, [C.c_int32] * 4 + [_P, C.c_int32, C.POINTER(C.c_int32)]),
     "gdb_eval_lpips": (C.c_int, [_P, _P, _P] + [C.c_int32] * 7 + [_P, C.c_int32, _P, C.c_size_t, _P, C.c_int64, _P]),
+    "gdb_mlp_backward_layout": (C.c_int, [_CFG, C.c_int32, C.c_int64, C.POINTER(C.c_size_t)]),
+    "gdb_mlp_backward": (C.c_int, [_CFG, _P, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "gdb_unpack_weight_grads": (C.c_int, [_CFG, _P, C.POINTER(_P)]),
+    "gdb_render_weights_backward": (C.c_int, [_CFG, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "gdb_accumulate_backward": (C.c_int, [_CFG, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -717,6 +717,84 @@ class HotPathEngine:
                                            self._stream()))
         return fm, dm, om
 
+    # ---- backward of the operator mirrors --------------------------------------
+    @staticmethod
+    def packed_grad_slices():
+        """(offset, shape) of the 18 tensors inside the packed fp32 section, in NERF_KEYS order (weight, bias per key):
+        the layout `gdb_pack_weights` writes and `gdb_mlp_backward` fills (every block aligned to 4 floats)."""
+        shapes = ((19, 4), (32, 57), (1, 32), (16, 32), (64, 24), (1, 64), (64, 111), (1, 64), (8, 64))
+        out, off = [], 0
+        for shp in shapes:
+            for s in (shp, (shp[0],)):
+                out.append((off, s))
+                off = (off + int(np.prod(s)) + 3) // 4 * 4
+        return out, (off + 63) // 64 * 64
+
+    def mlp_backward_layout(self, V: int, n: int):
+        """(workspace bytes, partials per launch, samples per tile) of `mlp_backward`."""
+        out = (C.c_size_t * 3)()
+        _lib.check(self.lib.gdb_mlp_backward_layout(C.byref(self.cfg), int(V), int(n), out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    @_on_device
+    def mlp_backward(self, vox_feat: torch.Tensor, rgbs_feat_dir: torch.Tensor, g_sigma: torch.Tensor, g_feat: torch.Tensor,
+                     total: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None, need_vox: bool = True,
+                     need_rfd: bool = True):
+        """Gradients of `mlp` -> (g_packed, g_vox or None, g_rgbs_feat_dir or None).  g_packed holds the gradient of the 18
+        tensors in the layout of the packed fp32 section (`packed_grad_slices`).  weights: the packed weights of the forward
+        (default: the engine's current ones)."""
+        weights = self.weights if weights is None else weights
+        if weights is None:
+            raise ValueError("load_weights() first")
+        V, n, P = rgbs_feat_dir.shape
+        _chk(rgbs_feat_dir, "rgbs_feat_dir", (V, n, self.P)); _chk(vox_feat, "vox_feat", (n, self.cfg.voxel_dim))
+        _chk(g_sigma, "g_sigma", (n,)); _chk(g_feat, "g_feat", (n, self.Q)); _chk(weights, "weights", (self._n_packed,))
+        if total is not None:
+            _chk(total, "total", (1,), torch.int64)
+        ws_bytes, _, _ = self.mlp_backward_layout(V, n)
+        n_fp32 = self.packed_grad_slices()[1]
+        g_packed = torch.empty((n_fp32,), device=self.device)
+        g_vox = torch.empty_like(vox_feat) if need_vox else None
+        g_rfd = torch.empty_like(rgbs_feat_dir) if need_rfd else None
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.gdb_mlp_backward(C.byref(self.cfg), weights.data_ptr(), V, vox_feat.data_ptr(), rgbs_feat_dir.data_ptr(),
+                                             _ptr(total), n, g_sigma.data_ptr(), g_feat.data_ptr(), g_packed.data_ptr(), _ptr(g_vox),
+                                             _ptr(g_rfd), ws.data_ptr(), ws_bytes, self._stream()))
+        return g_packed, g_vox, g_rfd
+
+    @_on_device
+    def render_weights_backward(self, sigma: torch.Tensor, indices: torch.Tensor, n_bundles: int, g_weights: torch.Tensor,
+                                total: Optional[torch.Tensor] = None) -> torch.Tensor:
+        n = sigma.shape[0]
+        _chk(sigma, "sigma", (n,)); _chk(indices, "indices", (n,), torch.int64); _chk(g_weights, "g_weights", (n,))
+        if total is not None:
+            _chk(total, "total", (1,), torch.int64)
+        g_sigma = torch.empty((n,), device=self.device)
+        scratch = torch.empty((2 * n_bundles,), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gdb_render_weights_backward(C.byref(self.cfg), sigma.data_ptr(), indices.data_ptr(), _ptr(total), n,
+                                                        n_bundles, g_weights.data_ptr(), g_sigma.data_ptr(), scratch.data_ptr(),
+                                                        self._stream()))
+        return g_sigma
+
+    @_on_device
+    def accumulate_backward(self, weights: torch.Tensor, feat: torch.Tensor, z_vals: torch.Tensor, indices: torch.Tensor, n_bundles: int,
+                            g_feat_map: torch.Tensor, g_depth_map: torch.Tensor, g_opacity_map: torch.Tensor,
+                            total: Optional[torch.Tensor] = None):
+        """Gradients of `accumulate` -> (g_weights (n,), g_feat (n, channels)); z_vals gets none."""
+        n, ch = feat.shape
+        _chk(weights, "weights", (n,)); _chk(feat, "feat", (n, ch)); _chk(z_vals, "z_vals", (n,)); _chk(indices, "indices", (n,), torch.int64)
+        _chk(g_feat_map, "g_feat_map", (n_bundles, ch)); _chk(g_depth_map, "g_depth_map", (n_bundles,))
+        _chk(g_opacity_map, "g_opacity_map", (n_bundles,))
+        if total is not None:
+            _chk(total, "total", (1,), torch.int64)
+        g_w, g_f = torch.empty((n,), device=self.device), torch.empty((n, ch), device=self.device)
+        scratch = torch.empty((2 * n_bundles,), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gdb_accumulate_backward(C.byref(self.cfg), weights.data_ptr(), feat.data_ptr(), z_vals.data_ptr(),
+                                                    indices.data_ptr(), _ptr(total), n, n_bundles, ch, g_feat_map.data_ptr(),
+                                                    g_depth_map.data_ptr(), g_opacity_map.data_ptr(), g_w.data_ptr(), g_f.data_ptr(),
+                                                    scratch.data_ptr(), self._stream()))
+        return g_w, g_f
+
     def render_unfused(self):
         """build_rays → sample → encode → MLP → composite through the operator mirrors (all fp32)."""
         s = self.sample()

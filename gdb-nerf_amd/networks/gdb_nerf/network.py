@@ -4,7 +4,13 @@ the checkpoint prefixes), same `forward(batch) -> (ret, mvs_depths, blend_rgbs)`
 
 The CNNs run on PyTorch-ROCm.  The hot-path section (reference network.py:145-169) runs on the HIP
 library: by default as ONE fused kernel (`gdb_render_bundles_fused`); with `hot_path = "mirrors"`
-through the operator mirrors, which materialise the reference's intermediates."""
+through the operator mirrors, which materialise the reference's intermediates.
+
+What is differentiable:
+  * `hot_path: "mirrors"`: the radiance MLP and the normalised alpha composite have HIP backward kernels, so
+    `forward(batch)[0]["rgb"].sum().backward()` fills the gradients of `nerf.*` and of `upsampler.*` (the PyTorch decoder module).
+  * `feature_net.*` and `depth_net.*` get none: `encode` (and `sample`) stay non-differentiable, their outputs carry no graph.
+  * `hot_path: "fused"` is unchanged and non-differentiable: its outputs have no `grad_fn` whatever `requires_grad` says."""
 from types import SimpleNamespace
 from typing import Any, Dict, List, Tuple
 

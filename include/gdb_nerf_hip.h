@@ -258,6 +258,41 @@ int gdb_accumulate(const GdbConfig* cfg, const float* d_weights, const float* d_
                    float* d_feat_map, float* d_depth_map, float* d_opacity_map, void* d_scratch_2xnbundles_i32,
                    void* stream);
 
+/* ---- backward of the operator mirrors (training) ----------------------- */
+/* Gradients of gdb_mlp, gdb_render_weights and gdb_accumulate, fp32.  Nothing is saved between forward and backward: every
+ * entry recomputes what it needs from the forward's inputs.  No floating-point atomics: results are bit-identical from run
+ * to run.  gdb_encode, the fused entries and the decoder have no backward.
+ *
+ * gdb_mlp_backward_layout: out[0] = workspace bytes of gdb_mlp_backward, out[1] = partials (workgroups) per launch,
+ * out[2] = samples per tile.  V < 2 is refused with GDB_E_SHAPE (the unbiased variance over views has no derivative there). */
+int gdb_mlp_backward_layout(const GdbConfig* cfg, int32_t V, int64_t n_alloc, size_t out[3]);
+
+/* d_g_sigma (n_alloc), d_g_feat (n_alloc, P-4+C_v): upstream gradients of gdb_mlp's outputs.  d_g_packed receives the gradient
+ * of all 18 tensors in the layout of the packed fp32 section (its first floats; gdb_unpack_weight_grads takes it apart; pad
+ * slots are zero, view_fc's slots are zero without viewdir_agg).  d_g_vox (n_alloc, C_v) and d_g_rgbs_feat_dir (V, n_alloc, P)
+ * may be NULL.  Rows [*d_total, n_alloc) add nothing to the weight gradients and get zero rows in both. */
+int gdb_mlp_backward(const GdbConfig* cfg, const float* d_packed_weights, int32_t V, const float* d_vox_feat,
+                     const float* d_rgbs_feat_dir, const int64_t* d_total, int64_t n_alloc, const float* d_g_sigma,
+                     const float* d_g_feat, float* d_g_packed, float* d_g_vox, float* d_g_rgbs_feat_dir, void* d_workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* Host inverse of gdb_pack_weights' fp32 section: copies each tensor's gradient out of h_packed (order and sizes as
+ * gdb_pack_weights; the two view_fc pointers are ignored without viewdir_agg). */
+int gdb_unpack_weight_grads(const GdbConfig* cfg, const float* h_packed, float* const h_tensors[18]);
+
+/* d_g_weights (n_alloc) -> d_g_sigma (n_alloc); samples of no bundle and rows past *d_total get 0.  The clamp of the weight
+ * sum at 1e-6 has derivative 0 below it. */
+int gdb_render_weights_backward(const GdbConfig* cfg, const float* d_sigma, const int64_t* d_indices, const int64_t* d_total,
+                                int64_t n_alloc, int64_t n_bundles, const float* d_g_weights, float* d_g_sigma,
+                                void* d_scratch_2xnbundles_i32, void* stream);
+
+/* d_g_feat_map (n_bundles, channels), d_g_depth_map, d_g_opacity_map (n_bundles) -> d_g_weights (n_alloc), d_g_feat (n_alloc,
+ * channels).  d_z_vals gets no gradient (it comes from the sampler).  d_scratch is not read by this version and may be NULL. */
+int gdb_accumulate_backward(const GdbConfig* cfg, const float* d_weights, const float* d_feat, const float* d_z_vals,
+                            const int64_t* d_indices, const int64_t* d_total, int64_t n_alloc, int64_t n_bundles, int32_t channels,
+                            const float* d_g_feat_map, const float* d_g_depth_map, const float* d_g_opacity_map,
+                            float* d_g_weights, float* d_g_feat, void* d_scratch_2xnbundles_i32, void* stream);
+
 /* ---- production entry ---------------------------------------------------------------- */
 /* The whole hot-path section of Network.forward (network.py:145-169: build_rays → sample →
  * encode → render_bundles) in one pass with no intermediate in HBM.  Needs gdb_prepare on
