@@ -90,6 +90,7 @@ class HotPathEngine:
         self._keep: Dict[str, torch.Tensor] = {}
         self._ws: Optional[torch.Tensor] = None
         self._plan_key = None
+        self.prepare_count = 0   # prepare() calls so far: what holds a frame across calls (EncodeFunction) sees a later prepare by it
         self._pyr16_ready = False
         self._pyr32_ready = True
         self._plan_static = False
@@ -212,6 +213,7 @@ class HotPathEngine:
         if self._ws is None or self._ws.numel() < need.value:
             self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         self._frame, self._keep = f, dict(frame)
+        self.prepare_count += 1
         self._fused_ok = None
         # gdb_prepare builds the dense schedule's plan from the depth prior as it is NOW (adaptive configs); a later render may
         # skip its own rebuild (GDB_SCHED_PLAN_READY) only while that tensor is unchanged: same storage, same version counter
@@ -794,6 +796,42 @@ class HotPathEngine:
                                                     g_depth_map.data_ptr(), g_opacity_map.data_ptr(), g_w.data_ptr(), g_f.data_ptr(),
                                                     scratch.data_ptr(), self._stream()))
         return g_w, g_f
+
+    # ---- backward of encode with respect to the gathered values -----------------
+    def encode_backward_layout(self, n: Optional[int] = None):
+        """(workspace bytes, fixed-point fraction bits F, byte offset of the pyramid accumulators, of the volume accumulators) of
+        `encode_backward` on the frame last prepared, for n allocated sample rows (default: n_bundles * S_max)."""
+        f = self._need_frame()
+        n = self.n_bundles * self.cfg.max_num_samples if n is None else int(n)
+        out = (C.c_size_t * 4)()
+        _lib.check(self.lib.gdb_encode_backward_layout(C.byref(self.cfg), C.byref(f), n, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    @_on_device
+    def encode_backward(self, rays_xyz: torch.Tensor, uvd: torch.Tensor, ball_radii: torch.Tensor, samples_per_batch: torch.Tensor,
+                        total: torch.Tensor, g_rfd: torch.Tensor, g_vox: torch.Tensor, need_img: bool = True, need_vol: bool = True):
+        """Gradients of `encode` on the frame last prepared with respect to the values it gathers -> (g_img_feat (B,V,C_f+3,H,W) or
+        None, g_feat_volume (B,C_v,D,H,W) or None).  The sample arrays are those `encode` was given; they, the cameras and the source
+        images get no gradient.  Two calls on the same inputs return bit-identical tensors (fixed-point accumulation)."""
+        f = self._need_frame()
+        if not (need_img or need_vol):
+            raise ValueError("encode_backward: neither output is asked for")
+        n = rays_xyz.shape[0]
+        bb = self.b * self.b
+        _chk(rays_xyz, "rays_xyz", (n, 3, bb)); _chk(uvd, "uvd", (n, 3)); _chk(ball_radii, "ball_radii", (n,))
+        _chk(samples_per_batch, "samples_per_batch", (f.B,), torch.int64); _chk(total, "total", (1,), torch.int64)
+        _chk(g_rfd, "g_rfd", (f.V, n, self.P)); _chk(g_vox, "g_vox", (n, self.cfg.voxel_dim))
+        need = self.encode_backward_layout(n)[0]
+        ws = getattr(self, "_enc_bwd_ws", None)   # one workspace per engine, grown on demand (the entry zeroes what it uses)
+        if ws is None or ws.numel() < need:
+            ws = self._enc_bwd_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        g_img = torch.empty((f.B, f.V, self.cfg.feat_dim + 3, f.H, f.W), device=self.device) if need_img else None
+        g_vol = torch.empty((f.B, self.cfg.voxel_dim, f.D, f.H, f.W), device=self.device) if need_vol else None
+        _lib.check(self.lib.gdb_encode_backward(C.byref(self.cfg), C.byref(f), self._ws.data_ptr(), rays_xyz.data_ptr(), uvd.data_ptr(),
+                                                ball_radii.data_ptr(), samples_per_batch.data_ptr(), total.data_ptr(), n,
+                                                g_rfd.data_ptr(), g_vox.data_ptr(), _ptr(g_img), _ptr(g_vol), ws.data_ptr(), ws.numel(),
+                                                self._stream()))
+        return g_img, g_vol
 
     def render_unfused(self):
         """build_rays → sample → encode → MLP → composite through the operator mirrors (all fp32)."""

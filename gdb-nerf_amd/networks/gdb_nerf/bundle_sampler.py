@@ -1,7 +1,11 @@
 """Depth-guided bundle sampler with the reference's method signatures
 (networks/gdb_nerf/bundle_sampler.py), every method backed by one entry of the C ABI:
 build_rays -> gdb_build_rays, sample -> gdb_sample, encode -> gdb_encode.  These materialise the
-reference's intermediates; `Network.forward` uses the fused kernel instead."""
+reference's intermediates; `Network.forward` uses the fused kernel instead.
+
+`encode` is differentiable with respect to the values it gathers (`img_feat`, `feat_volume`) when the sampler's `encode_grad` is set:
+the call then goes through `EncodeFunction`, whose backward is `gdb_encode_backward`.  The sample positions, the
+cameras and the source images get no gradient."""
 from typing import Dict, List, Tuple, Union
 
 import torch
@@ -9,10 +13,39 @@ import torch
 from ...engine import HotPathEngine
 
 
+class EncodeFunction(torch.autograd.Function):
+    """`gdb_encode` with `gdb_encode_backward` as its derivative with respect to img_feat and feat_volume.  Nothing but the inputs is
+    kept: the backward recomputes the coordinates.  `frame` holds the other tensors of the frame `encode` prepares; when the engine
+    has prepared anything since this forward (another frame's forward, for one), the backward prepares this frame again first."""
+
+    @staticmethod
+    def forward(ctx, engine, frame, img_feat, feat_volume, rays_xyz, uvd, ball_radii, samples_per_batch, total):
+        engine.prepare(dict(frame, img_feat=img_feat, feat_volume=feat_volume))
+        rfd, vox = engine.encode(rays_xyz, uvd, ball_radii, samples_per_batch, total)
+        ctx.engine, ctx.frame, ctx.prepared = engine, frame, engine.prepare_count
+        ctx.save_for_backward(img_feat, feat_volume, rays_xyz, uvd, ball_radii, samples_per_batch, total)
+        return rfd, vox
+
+    @staticmethod
+    def backward(ctx, g_rfd, g_vox):
+        img_feat, feat_volume, rays_xyz, uvd, ball_radii, samples_per_batch, total = ctx.saved_tensors
+        eng = ctx.engine
+        if eng.prepare_count != ctx.prepared:   # a stale camera block would scatter this frame's samples through another's cameras
+            eng.prepare(dict(ctx.frame, img_feat=img_feat, feat_volume=feat_volume))
+        n = rays_xyz.shape[0]
+        g_rfd = torch.zeros((img_feat.shape[1], n, eng.P), device=img_feat.device) if g_rfd is None else g_rfd.contiguous().float()
+        g_vox = torch.zeros((n, feat_volume.shape[1]), device=img_feat.device) if g_vox is None else g_vox.contiguous().float()
+        need_img, need_vol = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        g_img, g_vol = eng.encode_backward(rays_xyz, uvd, ball_radii, samples_per_batch, total, g_rfd, g_vox, need_img, need_vol)
+        return None, None, g_img, g_vol, None, None, None, None, None
+
+
 class BundleSampler:
-    def __init__(self, global_num_depth: int, max_mipmap_level: int) -> None:
+    def __init__(self, global_num_depth: int, max_mipmap_level: int, encode_grad: bool = False) -> None:
         self.global_num_depth = global_num_depth
         self.max_mipmap_level = max_mipmap_level
+        # nerf.encode_grad: `encode` carries a graph to img_feat / feat_volume (EncodeFunction); off: the calls of before
+        self.encode_grad = bool(encode_grad)
         self.H_orig = self.W_orig = None
         self.rays_o = self.rays_d = self.uv = self.tar_pixel_radius = self.z_axis = self.near = self.far = None
         self._tar = None
@@ -60,6 +93,13 @@ class BundleSampler:
         c = lambda t: t.contiguous().float()
         near_far = self._tar["near_far"] if self._tar is not None else torch.ones((B, 2), device=img_feat.device)
         dr = torch.ones((B, 2, H, W), device=img_feat.device)
+        if self.encode_grad and torch.is_grad_enabled() and any(t.is_cuda and t.requires_grad for t in (img_feat, feat_volume)):
+            frame = {"src_images": c(src_images).detach(), "depth_range": dr, "vol_range": dr, "src_exts": c(src_exts).detach(),
+                     "src_ints": c(src_ints).detach(), "tar_ext": c(tar_exts).detach(),
+                     "tar_int": self._tar["tar_int"] if self._tar else c(src_ints[:, 0]).detach(), "near_far": near_far}
+            total = torch.tensor([rays_xyz.shape[0]], dtype=torch.int64, device=img_feat.device)
+            return EncodeFunction.apply(eng, frame, c(img_feat), c(feat_volume), c(rays_xyz).detach(), c(uvd).detach(), c(ball_radii).detach(),
+                                        samples_per_batch.to(torch.int64).contiguous(), total)
         eng.prepare({"src_images": c(src_images), "img_feat": c(img_feat), "feat_volume": c(feat_volume), "depth_range": dr, "vol_range": dr,
                      "src_exts": c(src_exts), "src_ints": c(src_ints), "tar_ext": c(tar_exts), "tar_int": self._tar["tar_int"] if self._tar else c(src_ints[:, 0]),
                      "near_far": near_far})

@@ -6,10 +6,15 @@ The CNNs run on PyTorch-ROCm.  The hot-path section (reference network.py:145-16
 library: by default as ONE fused kernel (`gdb_render_bundles_fused`); with `hot_path = "mirrors"`
 through the operator mirrors, which materialise the reference's intermediates.
 
-What is differentiable (DESIGN.md 4.14):
+What is differentiable (DESIGN.md 4.14, 4.15):
   * `hot_path: "mirrors"`: the radiance MLP and the normalised alpha composite have HIP backward kernels, so
     `forward(batch)[0]["rgb"].sum().backward()` fills the gradients of `nerf.*` and of `upsampler.*` (the PyTorch decoder module).
-  * `feature_net.*` and `depth_net.*` get none: `encode` (and `sample`) stay non-differentiable, their outputs carry no graph.
+  * `feature_net.*` and `depth_net.*` get none by default: the outputs of `encode` (and `sample`) carry no graph.
+  * `nerf.encode_grad: true` (with `hot_path: "mirrors"`; default false): `encode` is differentiable with respect to the VALUES it
+    gathers, the feature map and the cost-regularised feature volume (`gdb_encode_backward`), so the colour loss also reaches
+    `feature_net.*` and the part of `depth_net.*` that produces the last stage's feature volume.  The sample POSITIONS stay constant:
+    `sample` has no backward, so nothing flows to the depth net through the depth prior, nor to the cameras or the source images.
+    With the HIP FPN / cost-regularisation / cascade switches on, those tensors carry no `grad_fn` and the plain calls are made.
   * `hot_path: "fused"` is unchanged and non-differentiable: its outputs have no `grad_fn` whatever `requires_grad` says."""
 from types import SimpleNamespace
 from typing import Any, Dict, List, Tuple
@@ -49,7 +54,12 @@ class Network(nn.Module):
         self.inv_depth = mvs.inv_depth[-1]
         self.is_adaptive = nrf.is_adaptive
         self.global_num_depth, self.max_mipmap_level = nrf.global_num_depth, nrf.max_mipmap_level
-        self.sampler = BundleSampler(self.global_num_depth, self.max_mipmap_level)
+        # nerf.encode_grad: `encode` differentiable with respect to the feature map and the feature volume; needs the
+        # operator mirrors, since the fused kernel carries no graph at all and the switch would train nothing, silently
+        self.encode_grad = bool(getattr(nrf, "encode_grad", False))
+        if self.encode_grad and getattr(nrf, "hot_path", "fused") != "mirrors":
+            raise ValueError(f"nerf.encode_grad needs nerf.hot_path 'mirrors' (got {getattr(nrf, 'hot_path', 'fused')!r}): the fused hot path is not differentiable")
+        self.sampler = BundleSampler(self.global_num_depth, self.max_mipmap_level, encode_grad=self.encode_grad)
 
         # pyramid level whose scale is closest to (not below) the bundle map's 1/b   (reference :40-43)
         self.feat_level = next((i for i, s in enumerate(fpn.feat_scales) if s >= 1.0 / self.b_size), len(fpn.feat_scales))

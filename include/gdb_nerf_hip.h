@@ -261,7 +261,8 @@ int gdb_accumulate(const GdbConfig* cfg, const float* d_weights, const float* d_
 /* ---- backward of the operator mirrors (training) ----------------------- */
 /* Gradients of gdb_mlp, gdb_render_weights and gdb_accumulate, fp32.  Nothing is saved between forward and backward: every
  * entry recomputes what it needs from the forward's inputs.  No floating-point atomics: results are bit-identical from run
- * to run.  gdb_encode, the fused entries and the decoder have no backward.
+ * to run.  gdb_encode has a backward with respect to the values it gathers (gdb_encode_backward below); gdb_sample, the
+ * fused entries and the decoder have none.
  *
  * gdb_mlp_backward_layout: out[0] = workspace bytes of gdb_mlp_backward, out[1] = partials (workgroups) per launch,
  * out[2] = samples per tile.  V < 2 is refused with GDB_E_SHAPE (the unbiased variance over views has no derivative there). */
@@ -292,6 +293,34 @@ int gdb_accumulate_backward(const GdbConfig* cfg, const float* d_weights, const 
                             const int64_t* d_indices, const int64_t* d_total, int64_t n_alloc, int64_t n_bundles, int32_t channels,
                             const float* d_g_feat_map, const float* d_g_depth_map, const float* d_g_opacity_map,
                             float* d_g_weights, float* d_g_feat, void* d_scratch_2xnbundles_i32, void* stream);
+
+/* ---- backward of gdb_encode with respect to the gathered values (ABI v7, added) ---- */
+/* With the sample positions held constant gdb_encode is linear in img_feat (through the 2x2 box mip chain and the
+ * linear-mipmap-linear fetch) and in feat_volume (trilinear, border): the backward is the transpose of the gather, a scatter-add.
+ * No gradient goes to d_rays_xyz, d_uvd, d_ball_radii, the cameras or d_src_images.
+ *
+ * Reproducible by fixed point, not by order: G = max |upstream| over the rows [0, *d_total) of d_g_vox and of the C_f + 3 feature
+ * columns of d_g_rgbs_feat_dir (both, whichever outputs are asked for); with e = ceil(log2 G) every contribution w * g is formed in
+ * double, scaled by 2^(F - e), rounded to a 64-bit integer and added with one integer atomic - integer addition is associative, so
+ * two calls on the same inputs give bit-identical outputs.  F = min(40, 62 - ceil(log2(8 n_alloc))): one destination receives at
+ * most 8 n_alloc contributions of magnitude <= 2^e (8 volume taps, or the 4 texture taps of one level when both axes clamp), so no
+ * sum leaves int64.  Absolute resolution of a contribution: 2^(e - F).  G == 0: the outputs are exact zeros.  G not finite (an inf or
+ * a NaN in a valid upstream row cannot be scaled): the requested outputs are filled with NaN.
+ *
+ * gdb_encode_backward_layout: out[0] = bytes of d_bwd_workspace, out[1] = F, out[2] / out[3] = byte offsets of the accumulators
+ * inside it - pyramid: int64 [B * V][level][y][x][20] with the level offsets of gdb_pyramid_layout (in texels of 20), channel 19 unused;
+ * volume: int64 [B][z][y][x][C_v].  n_alloc outside 1 .. B*H*W*S_max is GDB_E_SHAPE, out == NULL GDB_E_BADARG. */
+int gdb_encode_backward_layout(const GdbConfig* cfg, const GdbFrame* shape, int64_t n_alloc, size_t out[4]);
+
+/* d_workspace: the workspace gdb_prepare filled for THIS frame, read-only - its camera block and the level geometry are used, not
+ * the pyramid's contents; the frame's device pointers are not read.  The sample arrays are those gdb_encode was given.
+ * d_g_rgbs_feat_dir (V, n_alloc, P) and d_g_vox (n_alloc, C_v): upstream gradients of gdb_encode's outputs, both required.
+ * d_g_img_feat (B, V, C_f+3, H, W) and d_g_feat_volume (B, C_v, D, H, W): either may be NULL, and then its scatter is not run; both
+ * NULL is GDB_E_BADARG.  Rows [*d_total, n_alloc) contribute nothing, whatever they hold.  d_bwd_workspace is zeroed here. */
+int gdb_encode_backward(const GdbConfig* cfg, const GdbFrame* frame, const void* d_workspace, const float* d_rays_xyz,
+                        const float* d_uvd, const float* d_ball_radii, const int64_t* d_samples_per_batch, const int64_t* d_total,
+                        int64_t n_alloc, const float* d_g_rgbs_feat_dir, const float* d_g_vox, float* d_g_img_feat,
+                        float* d_g_feat_volume, void* d_bwd_workspace, size_t bwd_workspace_bytes, void* stream);
 
 /* ---- production entry ---------------------------------------------------------------- */
 /* The whole hot-path section of Network.forward (network.py:145-169: build_rays → sample →
