@@ -132,6 +132,8 @@ _SIGNATURES = {
     "gdb_accumulate_backward": (C.c_int, [_CFG, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "gdb_encode_backward_layout": (C.c_int, [_CFG, _FRM, C.c_int64, C.POINTER(C.c_size_t)]),
     "gdb_encode_backward": (C.c_int, [_CFG, _FRM, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "gdb_encode_position_backward": (C.c_int, [_CFG, _FRM, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "gdb_sample_backward": (C.c_int, [_CFG, _FRM, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

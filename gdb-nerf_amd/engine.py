@@ -833,6 +833,60 @@ class HotPathEngine:
                                                 self._stream()))
         return g_img, g_vol
 
+    # ---- backward of encode with respect to the sample positions, and of sample ------
+    @_on_device
+    def encode_position_backward(self, rays_xyz: torch.Tensor, uvd: torch.Tensor, ball_radii: torch.Tensor, samples_per_batch: torch.Tensor,
+                                 total: torch.Tensor, g_rfd: torch.Tensor, g_vox: torch.Tensor, need_rays: bool = True,
+                                 need_uvd: bool = True, need_ball: bool = True):
+        """Gradients of `encode` on the frame last prepared with respect to the sample positions -> (g_rays_xyz (n,3,b²), g_uvd (n,3),
+        g_ball_radii (n)), each None when not asked for.  Columns 0 and 1 of g_uvd are zeros: u, v are not differentiated.  The sample
+        arrays are those `encode` was given.  Two calls on the same inputs return bit-identical tensors (fixed summation order)."""
+        f = self._need_frame()
+        self._need_pyr32()
+        if not (need_rays or need_uvd or need_ball):
+            raise ValueError("encode_position_backward: no output is asked for")
+        n = rays_xyz.shape[0]
+        bb = self.b * self.b
+        _chk(rays_xyz, "rays_xyz", (n, 3, bb)); _chk(uvd, "uvd", (n, 3)); _chk(ball_radii, "ball_radii", (n,))
+        _chk(samples_per_batch, "samples_per_batch", (f.B,), torch.int64); _chk(total, "total", (1,), torch.int64)
+        _chk(g_rfd, "g_rfd", (f.V, n, self.P)); _chk(g_vox, "g_vox", (n, self.cfg.voxel_dim))
+        g_rays = torch.empty((n, 3, bb), device=self.device) if need_rays else None
+        g_uvd = torch.empty((n, 3), device=self.device) if need_uvd else None
+        g_ball = torch.empty((n,), device=self.device) if need_ball else None
+        _lib.check(self.lib.gdb_encode_position_backward(C.byref(self.cfg), C.byref(f), self._ws.data_ptr(), rays_xyz.data_ptr(),
+                                                         uvd.data_ptr(), ball_radii.data_ptr(), samples_per_batch.data_ptr(),
+                                                         total.data_ptr(), n, g_rfd.data_ptr(), g_vox.data_ptr(), _ptr(g_rays),
+                                                         _ptr(g_uvd), _ptr(g_ball), self._stream()))
+        return g_rays, g_uvd, g_ball
+
+    @_on_device
+    def sample_backward(self, samples_per_bundle: torch.Tensor, total: torch.Tensor, g_rays_xyz: Optional[torch.Tensor] = None,
+                        g_uvd: Optional[torch.Tensor] = None, g_z_vals: Optional[torch.Tensor] = None,
+                        g_ball_radii: Optional[torch.Tensor] = None, need_depth: bool = True, need_vol: bool = True):
+        """Gradients of `sample` on the frame last prepared (its depth_range / vol_range) -> (g_depth_range, g_vol_range), both
+        (B,2,H,W), each None when not asked for.  samples_per_bundle int32: the counts `sample` returned (data: no derivative).  The
+        upstream gradients have one row per sample; None = zero.  Bit-identical from call to call."""
+        f = self._need_frame()
+        ups = (g_rays_xyz, g_uvd, g_z_vals, g_ball_radii)
+        if all(g is None for g in ups):
+            raise ValueError("sample_backward: no upstream gradient is given")
+        if not (need_depth or need_vol):
+            raise ValueError("sample_backward: neither output is asked for")
+        n = next(g for g in ups if g is not None).shape[0]
+        bb = self.b * self.b
+        for g, name, shp in zip(ups, ("g_rays_xyz", "g_uvd", "g_z_vals", "g_ball_radii"), ((n, 3, bb), (n, 3), (n,), (n,))):
+            if g is not None:
+                _chk(g, name, shp)
+        nb = self.n_bundles
+        _chk(samples_per_bundle, "samples_per_bundle", (nb,), torch.int32); _chk(total, "total", (1,), torch.int64)
+        g_dr = torch.empty((f.B, 2, f.H, f.W), device=self.device) if need_depth else None
+        g_vr = torch.empty((f.B, 2, f.H, f.W), device=self.device) if need_vol else None
+        scratch = torch.empty((nb + (nb + 1023) // 1024,), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gdb_sample_backward(C.byref(self.cfg), C.byref(f), self._ws.data_ptr(), samples_per_bundle.data_ptr(),
+                                                total.data_ptr(), n, *(_ptr(g) for g in ups), _ptr(g_dr), _ptr(g_vr),
+                                                scratch.data_ptr(), self._stream()))
+        return g_dr, g_vr
+
     def render_unfused(self):
         """build_rays → sample → encode → MLP → composite through the operator mirrors (all fp32)."""
         s = self.sample()

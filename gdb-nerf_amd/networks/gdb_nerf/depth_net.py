@@ -83,6 +83,30 @@ def depth_regression(depth_values, depth_prob, ci_scale: float, inv_depth: bool)
     return mean, torch.cat((torch.max(mean - half, first), torch.min(mean + half, last)), 1)
 
 
+class HipDepthRegression(torch.autograd.Function):
+    """`gdb_depth_regression` (costvol.depth_regression) as the forward - the values every other path of the network sees - with the
+    derivative of `depth_regression` above as its backward: the soft-argmax, its standard deviation and the clipped interval are
+    recomputed from the saved inputs under autograd (a reduction over the hypotheses: not a hot path, no HIP backward is built for
+    it).  Taken only under `nerf.position_grad`, where the depth prior has to carry a graph to the 3-D U-Nets."""
+
+    @staticmethod
+    def forward(ctx, depth_values, depth_prob, ci_scale, inv_depth):
+        from ... import costvol
+        ctx.save_for_backward(depth_values, depth_prob)
+        ctx.ci_scale, ctx.inv_depth = ci_scale, inv_depth
+        return costvol.depth_regression(depth_values, depth_prob, ci_scale, inv_depth)
+
+    @staticmethod
+    def backward(ctx, g_depth, g_ci):
+        depth_values, depth_prob = ctx.saved_tensors
+        with torch.enable_grad():
+            hyp, prob = depth_values.detach().requires_grad_(), depth_prob.detach().requires_grad_()
+            depth, ci = depth_regression(hyp, prob, ctx.ci_scale, ctx.inv_depth)
+            outs, ups = zip(*((o, g) for o, g in ((depth, g_depth), (ci, g_ci)) if g is not None))
+            g_hyp, g_prob = torch.autograd.grad(outs, (hyp, prob), ups, allow_unused=True)
+        return (g_hyp if ctx.needs_input_grad[0] else None), (g_prob if ctx.needs_input_grad[1] else None), None, None
+
+
 class DepthNet(nn.Module):
     def __init__(self, config: SimpleNamespace) -> None:
         super().__init__()
@@ -101,6 +125,10 @@ class DepthNet(nn.Module):
         self._hip_regs = {}   # stage -> costvol.CostReg (not a module: no state-dict keys)
         # a whole stage as one library call (costvol.MvsStage): eval mode and fp32 CUDA inputs only; off by default
         self.hip_cascade = bool(getattr(mvs, "hip_cascade", False))
+        # nerf.position_grad: the depth prior must carry a graph to the 3-D U-Nets.  Under that switch - and only while
+        # grad mode is on and the probabilities require grad - gdb_depth_regression runs inside HipDepthRegression below: the same
+        # forward call, the same bits, with the derivative of the PyTorch formulation as its backward
+        self.position_grad = bool(getattr(config.nerf, "position_grad", False))
         # the reference indexes feat_dims by the pyramid level again (depth_net.py:32-37); kept for key/shape parity
         nets = [CostRegNet_small(self.feat_dims[self.vol_levels[0]], mvs.voxel_dim, fpn.base_channels)]
         nets += [CostRegNet(self.feat_dims[self.vol_levels[i]], mvs.voxel_dim, fpn.base_channels) for i in range(1, self.num_stages)]
@@ -171,7 +199,10 @@ class DepthNet(nn.Module):
                 hyp = hyp.contiguous()
                 cost = costvol.build_feature_volume(feats, src_exts, K_src, tar_exts, K_tar, hyp, self.inv_depth[s])
                 volume, prob = self._cost_reg(s, cost, feats)
-                depth, search = costvol.depth_regression(hyp, prob, self.ci_scales[s], self.inv_depth[s])
+                if self.position_grad and torch.is_grad_enabled() and prob.requires_grad:
+                    depth, search = HipDepthRegression.apply(hyp, prob, self.ci_scales[s], self.inv_depth[s])
+                else:
+                    depth, search = costvol.depth_regression(hyp, prob, self.ci_scales[s], self.inv_depth[s])
             else:
                 cost = build_feature_volume(feats, src_exts, K_src, tar_exts, K_tar, hyp, self.inv_depth[s])
                 volume, prob = self._cost_reg(s, cost, feats)

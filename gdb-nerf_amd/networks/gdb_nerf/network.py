@@ -6,15 +6,18 @@ The CNNs run on PyTorch-ROCm.  The hot-path section (reference network.py:145-16
 library: by default as ONE fused kernel (`gdb_render_bundles_fused`); with `hot_path = "mirrors"`
 through the operator mirrors, which materialise the reference's intermediates.
 
-What is differentiable (DESIGN.md 4.14, 4.15):
+What is differentiable (DESIGN.md 4.14, 4.15, 4.16):
   * `hot_path: "mirrors"`: the radiance MLP and the normalised alpha composite have HIP backward kernels, so
     `forward(batch)[0]["rgb"].sum().backward()` fills the gradients of `nerf.*` and of `upsampler.*` (the PyTorch decoder module).
   * `feature_net.*` and `depth_net.*` get none by default: the outputs of `encode` (and `sample`) carry no graph.
   * `nerf.encode_grad: true` (with `hot_path: "mirrors"`; default false): `encode` is differentiable with respect to the VALUES it
     gathers, the feature map and the cost-regularised feature volume (`gdb_encode_backward`), so the colour loss also reaches
-    `feature_net.*` and the part of `depth_net.*` that produces the last stage's feature volume.  The sample POSITIONS stay constant:
-    `sample` has no backward, so nothing flows to the depth net through the depth prior, nor to the cameras or the source images.
+    `feature_net.*` and the part of `depth_net.*` that produces the last stage's feature volume.  The sample POSITIONS stay constant.
     With the HIP FPN / cost-regularisation / cascade switches on, those tensors carry no `grad_fn` and the plain calls are made.
+  * `nerf.position_grad: true` (with `hot_path: "mirrors"`; default false; independent of `encode_grad`): the sample positions are
+    differentiable (`gdb_sample_backward`, `gdb_encode_position_backward`), so the colour loss - and `nerf_depth`,
+    through `z_vals` - reaches `depth_net.*` through `depth_range` / `vol_range`: the depth prior moves the samples, as in the
+    reference.  The cameras, the source images and `near_far` get no gradient.
   * `hot_path: "fused"` is unchanged and non-differentiable: its outputs have no `grad_fn` whatever `requires_grad` says."""
 from types import SimpleNamespace
 from typing import Any, Dict, List, Tuple
@@ -59,7 +62,12 @@ class Network(nn.Module):
         self.encode_grad = bool(getattr(nrf, "encode_grad", False))
         if self.encode_grad and getattr(nrf, "hot_path", "fused") != "mirrors":
             raise ValueError(f"nerf.encode_grad needs nerf.hot_path 'mirrors' (got {getattr(nrf, 'hot_path', 'fused')!r}): the fused hot path is not differentiable")
-        self.sampler = BundleSampler(self.global_num_depth, self.max_mipmap_level, encode_grad=self.encode_grad)
+        # nerf.position_grad: `sample` and the coordinate arithmetic of `encode` differentiable, so that the colour loss moves the depth
+        # prior that places the samples; independent of encode_grad, and refused without the mirrors for the same reason
+        self.position_grad = bool(getattr(nrf, "position_grad", False))
+        if self.position_grad and getattr(nrf, "hot_path", "fused") != "mirrors":
+            raise ValueError(f"nerf.position_grad needs nerf.hot_path 'mirrors' (got {getattr(nrf, 'hot_path', 'fused')!r}): the fused hot path is not differentiable")
+        self.sampler = BundleSampler(self.global_num_depth, self.max_mipmap_level, encode_grad=self.encode_grad, position_grad=self.position_grad)
 
         # pyramid level whose scale is closest to (not below) the bundle map's 1/b   (reference :40-43)
         self.feat_level = next((i for i, s in enumerate(fpn.feat_scales) if s >= 1.0 / self.b_size), len(fpn.feat_scales))

@@ -1,7 +1,8 @@
 """Volume-integration operators of the hot path with the reference's signatures
 (networks/gdb_nerf/utils.py:19-43, 88-121), backed by `gdb_render_weights` / `gdb_accumulate`.  When grad mode is on and an
 input requires grad, the calls go through the autograd Functions below (`gdb_render_weights_backward`,
-`gdb_accumulate_backward`); `z_vals` and the indices get no gradient."""
+`gdb_accumulate_backward`); `z_vals` gets weights * g_depth_map[indices], formed in torch, when it requires grad; the indices get
+no gradient."""
 from typing import Optional, Tuple
 
 import torch
@@ -47,7 +48,9 @@ class AccumulateFunction(torch.autograd.Function):
         g_depth_map = torch.zeros((nb,), device=dev) if g_depth_map is None else g_depth_map.contiguous()
         g_opacity_map = torch.zeros((nb,), device=dev) if g_opacity_map is None else g_opacity_map.contiguous()
         g_w, g_f = _engine(dev).accumulate_backward(weights, feat, z_vals, ray_indices, nb, g_feat_map, g_depth_map, g_opacity_map)
-        return g_w, g_f, None, None, None
+        # depth_map = segmented sum of weights * z: the path of `nerf_depth` to the depth net once z_vals carries a graph
+        g_z = weights * g_depth_map[ray_indices] if ctx.needs_input_grad[2] else None
+        return g_w, g_f, g_z, None, None
 
 
 def _wants_grad(*tensors) -> bool:
@@ -74,6 +77,6 @@ def render_weight_from_density(sigma: torch.Tensor, ray_indices: torch.Tensor, n
 def accumulate_value_along_rays(feat: torch.Tensor, z_vals: torch.Tensor, weights: torch.Tensor, ray_indices: torch.Tensor,
                                 num_rays: int, inverse_indices: Optional[torch.Tensor] = None):
     """Segmented sum of weights · [feat | z | 1] per bundle -> (feat_map, depth_map, opacity_map) (`gdb_accumulate`)."""
-    if _wants_grad(weights, feat):
+    if _wants_grad(weights, feat, z_vals):
         return AccumulateFunction.apply(weights.contiguous(), feat.contiguous(), z_vals.contiguous(), ray_indices.contiguous(), int(num_rays))
     return _engine(feat.device).accumulate(weights.contiguous(), feat.contiguous(), z_vals.contiguous(), ray_indices.contiguous(), int(num_rays))

@@ -261,8 +261,9 @@ int gdb_accumulate(const GdbConfig* cfg, const float* d_weights, const float* d_
 /* ---- backward of the operator mirrors (training) ----------------------- */
 /* Gradients of gdb_mlp, gdb_render_weights and gdb_accumulate, fp32.  Nothing is saved between forward and backward: every
  * entry recomputes what it needs from the forward's inputs.  No floating-point atomics: results are bit-identical from run
- * to run.  gdb_encode has a backward with respect to the values it gathers (gdb_encode_backward below); gdb_sample, the
- * fused entries and the decoder have none.
+ * to run.  gdb_encode has a backward with respect to the values it gathers (gdb_encode_backward below) and one with
+ * respect to the sample positions (gdb_encode_position_backward), gdb_sample one with respect to the depth prior (gdb_sample_backward;
+ * DESIGN.md 4.16); the fused entries and the decoder have none.
  *
  * gdb_mlp_backward_layout: out[0] = workspace bytes of gdb_mlp_backward, out[1] = partials (workgroups) per launch,
  * out[2] = samples per tile.  V < 2 is refused with GDB_E_SHAPE (the unbiased variance over views has no derivative there). */
@@ -288,7 +289,8 @@ int gdb_render_weights_backward(const GdbConfig* cfg, const float* d_sigma, cons
                                 void* d_scratch_2xnbundles_i32, void* stream);
 
 /* d_g_feat_map (n_bundles, channels), d_g_depth_map, d_g_opacity_map (n_bundles) -> d_g_weights (n_alloc), d_g_feat (n_alloc,
- * channels).  d_z_vals gets no gradient (it comes from the sampler).  d_scratch is not read by this version and may be NULL. */
+ * channels).  This entry gives d_z_vals no gradient: it is weights * g_depth_map[indices], which the Python AccumulateFunction forms
+ * in torch when z_vals carries a graph.  d_scratch is not read by this version and may be NULL. */
 int gdb_accumulate_backward(const GdbConfig* cfg, const float* d_weights, const float* d_feat, const float* d_z_vals,
                             const int64_t* d_indices, const int64_t* d_total, int64_t n_alloc, int64_t n_bundles, int32_t channels,
                             const float* d_g_feat_map, const float* d_g_depth_map, const float* d_g_opacity_map,
@@ -297,7 +299,8 @@ int gdb_accumulate_backward(const GdbConfig* cfg, const float* d_weights, const 
 /* ---- backward of gdb_encode with respect to the gathered values (ABI v7, added) ---- */
 /* With the sample positions held constant gdb_encode is linear in img_feat (through the 2x2 box mip chain and the
  * linear-mipmap-linear fetch) and in feat_volume (trilinear, border): the backward is the transpose of the gather, a scatter-add.
- * No gradient goes to d_rays_xyz, d_uvd, d_ball_radii, the cameras or d_src_images.
+ * This entry gives no gradient to d_rays_xyz, d_uvd and d_ball_radii (gdb_encode_position_backward below does); the cameras and
+ * d_src_images get none anywhere.
  *
  * Reproducible by fixed point, not by order: G = max |upstream| over the rows [0, *d_total) of d_g_vox and of the C_f + 3 feature
  * columns of d_g_rgbs_feat_dir (both, whichever outputs are asked for); with e = ceil(log2 G) every contribution w * g is formed in
@@ -321,6 +324,50 @@ int gdb_encode_backward(const GdbConfig* cfg, const GdbFrame* frame, const void*
                         const float* d_uvd, const float* d_ball_radii, const int64_t* d_samples_per_batch, const int64_t* d_total,
                         int64_t n_alloc, const float* d_g_rgbs_feat_dir, const float* d_g_vox, float* d_g_img_feat,
                         float* d_g_feat_volume, void* d_bwd_workspace, size_t bwd_workspace_bytes, void* stream);
+
+/* ---- backward of gdb_encode with respect to the sample positions, and of gdb_sample (ABI v7, added) ---- */
+/* Derivative conventions of both entries (what torch autograd of the plain-torch restatement does):
+ *  - tap indices, fractions, the mip level and every clamp decision are the forward's own bits (the forward's helpers, called in the
+ *    same order under the same compile contract); the derivative arithmetic runs in double and is rounded to float once per output.
+ *  - d/dx of a bilinear / trilinear fetch is (1 - f_y)(t01 - t00) + f_y (t11 - t10), times the coordinate scale: W_o / 2 for the
+ *    sub-ray colours, W_l per mip level for the feature texture, D / 2 for the volume's depth axis.  A coordinate clamped by border /
+ *    clamp-to-edge addressing has derivative 0, equality included (torch's grid_sample rule).
+ *  - the mip level clamped to [0, L] passes its derivative inside the interval and 0 outside; a NaN level gives 0.  d out / d level is
+ *    tex(l1) - tex(l0) where the blend fraction was used; both blended levels contribute to d / d(u, v) with their blend weights.
+ *  - clamp_min floors (1e-6 on the two projected depths, 1e-12 under the two square roots of the mip level, 1e-12 in the ball radius
+ *    per unit distance and in F.normalize): derivative 0 below the floor.
+ *  - no floating-point atomics and no order that depends on arrival: two calls on the same inputs give bit-identical outputs.
+ *
+ * gdb_encode_position_backward.  d_workspace: the workspace gdb_prepare filled for THIS frame.  Unlike gdb_encode_backward this entry
+ * reads the pyramid's contents, the frame's feature volume and its source images: the derivative of a bilinear fetch is a
+ * difference of the fetched texels.  The sample arrays and the two upstream gradients are those of gdb_encode_backward.
+ * Outputs d_g_rays_xyz (n_alloc, 3, b*b), d_g_uvd (n_alloc, 3), d_g_ball_radii (n_alloc): each may be NULL, all three NULL is
+ * GDB_E_BADARG.  Rows [*d_total, n_alloc) of every output are written as zeros and are never read, whatever they hold.  n_alloc
+ * outside 1 .. B*H*W*S_max is GDB_E_SHAPE.
+ * Columns 0 and 1 of d_g_uvd are written as zeros and are NOT differentiated: u, v are the bundle's pixel centre, depend on no
+ * trainable tensor and sit exactly on voxel centres, where the trilinear derivative is one-sided.  Column 2 is the gradient of the
+ * normalised depth.  Per view: sub-ray point -> camera -> image -> the colour taps (3 b*b columns, each sub-ray its own path);
+ * centre mean_s(E p_s) -> (u, v, level) -> the C_f + 3 feature columns (d_ball_radii enters through the level only); centre
+ * mean_s p_s -> the four direction columns.  d_g_rays_xyz[i, :, s] is the sum of the three paths over the views v = 0 .. V-1 in
+ * that order. */
+int gdb_encode_position_backward(const GdbConfig* cfg, const GdbFrame* frame, const void* d_workspace, const float* d_rays_xyz,
+                                 const float* d_uvd, const float* d_ball_radii, const int64_t* d_samples_per_batch,
+                                 const int64_t* d_total, int64_t n_alloc, const float* d_g_rgbs_feat_dir, const float* d_g_vox,
+                                 float* d_g_rays_xyz, float* d_g_uvd, float* d_g_ball_radii, void* stream);
+
+/* gdb_sample_backward.  d_workspace: prepared for the frame gdb_sample ran on (its target camera; the frame's d_depth_range /
+ * d_vol_range are read).  d_samples_per_bundle int32 (B*H*W): the counts gdb_sample returned - they are data: the derivative of
+ * ceil / clamp is 0; the sample offsets come from the same exclusive scan of them.  Upstream gradients of gdb_sample's outputs,
+ * n_alloc rows each, each may be NULL (= zero): d_g_rays_xyz (n_alloc, 3, b*b), d_g_uvd (n_alloc, 3; only column 2 is read),
+ * d_g_z_vals, d_g_ball_radii (n_alloc); all four NULL is GDB_E_BADARG.  Outputs d_g_depth_range, d_g_vol_range (B, 2, H, W): either
+ * may be NULL, both NULL is GDB_E_BADARG.  One bundle's four scalars receive the sum over its <= S_max samples in sample order; rows
+ * [*d_total, n_alloc) are not read.  Chain: t_k = n + (f - n)(k + 1/2) / c in sampling space; d = 2 (t - v_n) / (v_f - v_n) - 1;
+ * z = t, or 1 / t under inv_depth; rays_xyz = o + dir z; ball = unit |mean dir| |z|; under inv_depth the four ranges are inverted
+ * first (-1 / x^2 on the way back).  d_scratch: 4 * (B*H*W + ceil(B*H*W / 1024)) bytes. */
+int gdb_sample_backward(const GdbConfig* cfg, const GdbFrame* frame, const void* d_workspace, const int32_t* d_samples_per_bundle,
+                        const int64_t* d_total, int64_t n_alloc, const float* d_g_rays_xyz, const float* d_g_uvd,
+                        const float* d_g_z_vals, const float* d_g_ball_radii, float* d_g_depth_range, float* d_g_vol_range,
+                        void* d_scratch, void* stream);
 
 /* ---- production entry ---------------------------------------------------------------- */
 /* The whole hot-path section of Network.forward (network.py:145-169: build_rays → sample →
