@@ -134,6 +134,9 @@ _SIGNATURES = {
     "gdb_encode_backward": (C.c_int, [_CFG, _FRM, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "gdb_encode_position_backward": (C.c_int, [_CFG, _FRM, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "gdb_sample_backward": (C.c_int, [_CFG, _FRM, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdb_loss_workspace_bytes": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_size_t)]),
+    "gdb_photometric_loss": (C.c_int, [_P, _P] + [C.c_int64] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_float, _P, _P, C.c_size_t, _P, _P]),
+    "gdb_smooth_l1_masked": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_size_t, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -783,6 +783,40 @@ int gdb_mvs_stage(const float* d_src_feat, const float* d_src_exts, const float*
 int gdb_mvs_hypotheses(const float* d_range, int32_t hr, int32_t wr, double ratio, int32_t B, int32_t D, int32_t Ht, int32_t Wt,
                        int32_t inv_depth, float* d_out, void* stream);
 
+/* ---- the training loss: MSE + SSIM value and gradient, and the depth monitor (ABI v7, added) ---------------------------------
+ * The photometric loss of train/losses/gdb_nerf.py without its perceptual term, as one call that leaves the value and the gradient
+ * with respect to the estimate on the device.  Nothing is copied to the host, nothing waits, the library allocates nothing.
+ *
+ * Definition, all per-pixel arithmetic in fp32.  x1 = the ground truth, x2 = the estimate, both (B, 3, H, W); n = 3 B H W.
+ *   window: w = g (x) g with g_i = exp(-(i - 3)^2 / 4.5) / sum_j exp(-(j - 3)^2 / 4.5), i = 0 .. 6 (7 x 7 Gaussian, sigma 1.5; g itself
+ *     evaluated in fp32, so its taps sum to 1 + 3.7e-8 as torch's do), applied
+ *     per channel with zero padding 3: the image is zero outside, the window is NOT renormalised at the border;
+ *   m1 = w * x1, m2 = w * x2, e11 = w * x1^2, e22 = w * x2^2, e12 = w * (x1 x2);  s1 = e11 - m1^2, s2 = e22 - m2^2, s12 = e12 - m1 m2;
+ *   C1 = 1e-4, C2 = 9e-4;  N1 = 2 m1 m2 + C1, N2 = 2 s12 + C2, D1 = m1^2 + m2^2 + C1, D2 = s1 + s2 + C2;  S = N1 N2 / (D1 D2);
+ *   mse = sum (x1 - x2)^2 / n,  ssim = sum S / n,  photo = alpha mse + beta (1 - ssim).  No clamp, no mask.
+ * Gradient with respect to x2:  Bm = -S / D2,  Cm = 2 N1 / (D1 D2),  Am = 2 m1 N2 / (D1 D2) - 2 m2 S / D1 - 2 m2 Bm - m1 Cm, the three
+ *   maps zero outside the image;  d(sum S) / d x2 = w * Am + 2 x2 (w * Bm) + x1 (w * Cm) (the zero-padded symmetric window is its own
+ *   adjoint);  G = alpha 2 (x2 - x1) / n - (beta / n) d(sum S) / d x2.
+ * Sums over pixels in fp64: one partial pair per workgroup in d_workspace, added in a fixed order by a one-workgroup launch that
+ * writes the fp32 results.  No atomics: bit-identical from call to call, whatever d_workspace, d_grad and d_out3 held before.
+ *
+ * gdb_loss_workspace_bytes: enough for gdb_photometric_loss on (B, 3, H, W) and for gdb_smooth_l1_masked on B H W elements.
+ * gdb_photometric_loss: d_est (B, 3, H, W) contiguous; d_gt read in place at element strides (gt_sb, gt_sc, gt_sy, gt_sx), none
+ *   negative: (3 H W, H W, W, 1) for NCHW, (3 H W, 1, 3 W, 3) for the (B, H, W, 3) frames a data loader hands over.  d_grad (B, 3, H, W)
+ *   receives G, or NULL: the adjoint half is then not run (evaluation) and d_out3 holds the same bits.  d_out3 = [mse, ssim, photo].
+ * gdb_smooth_l1_masked (the monitor of train/losses/gdb_nerf.py, forward only): d_out1[0] = the mean over the elements with
+ *   mask > 0.5 of smooth-L1(est - gt) with beta 1 (0.5 d^2 for |d| < 1, else |d| - 0.5); 0 / 0 = NaN for an empty mask, as the mean of
+ *   an empty tensor is.  d_est, d_gt, d_mask: n contiguous floats each.
+ * Refused before any launch: B, H or W < 1, n < 1, or sizes the launch grid cannot hold (GDB_E_SHAPE); a NULL required pointer, a
+ * negative stride or a workspace that is too small (GDB_E_BADARG). */
+int gdb_loss_workspace_bytes(int32_t B, int32_t H, int32_t W, size_t* out_bytes);
+int gdb_photometric_loss(const float* d_est /* (B,3,H,W) contiguous */, const float* d_gt, int64_t gt_sb, int64_t gt_sc,
+                         int64_t gt_sy, int64_t gt_sx /* element strides: NCHW or the permuted NHWC view */,
+                         int32_t B, int32_t H, int32_t W, float alpha, float beta, float* d_grad /* (B,3,H,W) or NULL */,
+                         void* d_workspace, size_t ws_bytes, float* d_out3 /* mse, ssim, photo */, void* stream);
+int gdb_smooth_l1_masked(const float* d_est, const float* d_gt, const float* d_mask, int64_t n,
+                         void* d_workspace, size_t ws_bytes, float* d_out1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
