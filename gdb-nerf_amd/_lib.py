@@ -137,6 +137,12 @@ _SIGNATURES = {
     "gdb_loss_workspace_bytes": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_size_t)]),
     "gdb_photometric_loss": (C.c_int, [_P, _P] + [C.c_int64] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_float, _P, _P, C.c_size_t, _P, _P]),
     "gdb_smooth_l1_masked": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_size_t, _P, _P]),
+    "gdb_stage_nerf_packed_floats": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_size_t)]),
+    "gdb_pack_stage_nerf_weights": (C.c_int, [C.c_int32] * 4 + [C.POINTER(_P), _P]),
+    "gdb_unpack_stage_nerf_grads": (C.c_int, [C.c_int32] * 4 + [_P, C.POINTER(_P)]),
+    "gdb_stage_nerf_layout": (C.c_int, [C.c_int32] * 6 + [C.c_int64, C.POINTER(C.c_size_t)]),
+    "gdb_stage_nerf": (C.c_int, [C.c_int32] * 4 + [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "gdb_stage_nerf_backward": (C.c_int, [C.c_int32] * 4 + [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_size_t, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

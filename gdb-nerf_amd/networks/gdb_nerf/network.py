@@ -18,7 +18,10 @@ What is differentiable:
     differentiable (`gdb_sample_backward`, `gdb_encode_position_backward`), so the colour loss - and `nerf_depth`,
     through `z_vals` - reaches `depth_net.*` through `depth_range` / `vol_range`: the depth prior moves the samples, as in the
     reference.  The cameras, the source images and `near_far` get no gradient.
-  * `hot_path: "fused"` is unchanged and non-differentiable: its outputs have no `grad_fn` whatever `requires_grad` says."""
+  * `hot_path: "fused"` is unchanged and non-differentiable: its outputs have no `grad_fn` whatever `requires_grad` says.
+  * `mvs.stage_render: true` (training mode; independent of the hot path): `blend_rgbs` holds the depth net's stage images, whose loss
+    reaches `depth_net.nerfs.*`, `depth_net.cost_regs[i]` through the stage's feature volume and `feature_net.*` through the gathered
+    feature map."""
 from types import SimpleNamespace
 from typing import Any, Dict, List, Tuple
 

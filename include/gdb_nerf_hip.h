@@ -817,6 +817,41 @@ int gdb_photometric_loss(const float* d_est /* (B,3,H,W) contiguous */, const fl
 int gdb_smooth_l1_masked(const float* d_est, const float* d_gt, const float* d_mask, int64_t n,
                          void* d_workspace, size_t ws_bytes, float* d_out1, void* stream);
 
+/* ---- the depth net's train-time stage render: auxiliary NeRF + un-normalised composite, forward and backward (ABI v7, added;
+ * DESIGN.md 4.18) ----------------------------------------------------------------------------------------------------------------
+ * The per-stage NeRF of the reference's DepthNet (networks/gdb_nerf/depth_net.py:201-298) on materialised samples, and the composite
+ * of its _render_rays (:109-114): alpha = 1 - e^-sigma, T_i = prod_{j<i} (1 - alpha_j + 1e-10), rgb_map = sum_i alpha_i T_i c_i, not
+ * normalised.  The batch is folded into n_rays; ray r owns the samples [r S, (r + 1) S).
+ * Accepted (anything else is refused before the first launch): feat_dim 8, 16 or 32, voxel_dim 8, hid_dim 64, viewdir_agg 0 or 1
+ * (GDB_E_BADARG otherwise); 2 <= V <= GDB_MAX_VIEWS (V < 2: GDB_E_SHAPE, as gdb_mlp_backward_layout), 1 <= S <= GDB_MAX_SAMPLES,
+ * V * ceil4(S) <= 64 - a tile holds whole rays and at most 64 (view, sample) rows, a view's block padded to a multiple of four
+ * samples - and 1 <= n_rays < 2^31 / S (GDB_E_SHAPE otherwise).
+ * gdb_stage_nerf_packed_floats / gdb_pack_stage_nerf_weights / gdb_unpack_stage_nerf_grads (host only): the packed fp32 buffer of the 16
+ *   tensors view_fc.0, global_fc.0, agg_w_fc.0, fc.0, lr0.0, sigma.0, color.0, color.2 - weight then bias each, host pointers, row-major
+ *   as nn.Linear stores them.  Without viewdir_agg the first two pointers are not read (not written by unpack) and view_fc's slots
+ *   are zero.  Pad slots are zero.  The gradient buffer of gdb_stage_nerf_backward has the same layout.
+ * gdb_stage_nerf_layout: out[0] = workspace bytes of gdb_stage_nerf_backward, out[1] = partials (workgroups) per launch, out[2] = rays
+ *   per tile.
+ * gdb_stage_nerf: d_vox (n_rays*S, 8); d_img (n_rays*S, V, feat_dim+3+4), the reference's sample-major layout; d_rgb_map (n_rays, 3);
+ *   d_sigma (n_rays*S) and d_rgb (n_rays*S, 3) optional (NULL: not written).  One launch.
+ * gdb_stage_nerf_backward: the same inputs and d_g_rgb_map (n_rays, 3) -> d_g_packed (the packed layout, overwritten), d_g_vox and
+ *   d_g_img (shapes of d_vox / d_img; either may be NULL).  Nothing is saved by the forward: activations are recomputed per tile.
+ *   Weight gradients accumulate in registers over a workgroup's tiles; each workgroup writes one partial to d_workspace and a second
+ *   launch adds the partials in workgroup order in double: no floating-point atomics, bit-identical from run to run.  The workspace's
+ *   contents on entry do not matter.  A short workspace is GDB_E_WORKSPACE, a NULL required pointer GDB_E_BADARG. */
+int gdb_stage_nerf_packed_floats(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim, int32_t viewdir_agg, size_t* out_floats);
+int gdb_pack_stage_nerf_weights(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim, int32_t viewdir_agg,
+                                const float* const h_tensors[16], float* h_out);
+int gdb_unpack_stage_nerf_grads(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim, int32_t viewdir_agg,
+                                const float* h_packed, float* const h_tensors[16]);
+int gdb_stage_nerf_layout(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim, int32_t viewdir_agg, int32_t V, int32_t S,
+                          int64_t n_rays, size_t out[3]);
+int gdb_stage_nerf(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim, int32_t viewdir_agg, const float* d_packed, int32_t V, int32_t S,
+                   const float* d_vox, const float* d_img, int64_t n_rays, float* d_rgb_map, float* d_sigma, float* d_rgb, void* stream);
+int gdb_stage_nerf_backward(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim, int32_t viewdir_agg, const float* d_packed, int32_t V,
+                            int32_t S, const float* d_vox, const float* d_img, int64_t n_rays, const float* d_g_rgb_map, float* d_g_packed,
+                            float* d_g_vox, float* d_g_img, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
