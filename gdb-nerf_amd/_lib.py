@@ -54,6 +54,12 @@ class GdbDecRegion(C.Structure):
     _fields_ = [("name", C.c_char * 16), ("offset", C.c_uint64), ("bytes", C.c_uint64), ("shape", C.c_int32 * 4)]
 
 
+class GdbCostRegTrainRegion(C.Structure):
+    """A named region of the train-mode cost-reg saved buffer (buffer 0) or backward workspace (buffer 1) (gdb_cost_reg_train_layout)."""
+    _fields_ = [("name", C.c_char * 32), ("offset", C.c_uint64), ("bytes", C.c_uint64), ("buffer", C.c_int32), ("channels", C.c_int32),
+                ("level", C.c_int32), ("reserved", C.c_int32)]
+
+
 class GdbError(RuntimeError):
     pass
 
@@ -143,6 +149,10 @@ _SIGNATURES = {
     "gdb_stage_nerf_layout": (C.c_int, [C.c_int32] * 6 + [C.c_int64, C.POINTER(C.c_size_t)]),
     "gdb_stage_nerf": (C.c_int, [C.c_int32] * 4 + [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "gdb_stage_nerf_backward": (C.c_int, [C.c_int32] * 4 + [_P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "gdb_cost_reg_train_layout": (C.c_int, [C.c_int32] * 8 + [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "gdb_cost_reg_train": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 4 + [C.POINTER(_P), C.c_float, C.c_float, _P, C.c_size_t, _P, _P, _P, _P]),
+    "gdb_cost_reg_train_backward": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 4 + [C.POINTER(_P), _P, _P, _P, C.c_size_t, _P, C.c_size_t,
+                                                C.POINTER(_P), _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -23,6 +23,8 @@ DEFAULTS = {
     "test": {"batch_size": 1, "collator": "default", "epoch": -1, "batch_sampler": "default",
              "sampler_meta": {"input_views_num": [], "input_views_prob": []}, "eval_depth": False, "eval_center": False,
              "hip_metrics": False, "lpips_weights": ""},
+    # hip_cost_reg_train: the 3-D U-Nets in training mode, forward and backward, on the HIP library (costvol.CostRegTrain)
+    "mvs": {"hip_cost_reg_train": False},
 }
 
 

@@ -119,6 +119,122 @@ class CostReg:
         return volume, prob
 
 
+def cost_reg_train_layout(depth: int, cin: int, c: int, cout: int, B: int, D: int, H: int, W: int):
+    """gdb_cost_reg_train_layout (host only): ({(buffer, name): (offset, bytes, channels, level)}, saved bytes, workspace bytes);
+    buffer 0 is the saved buffer, 1 the backward's workspace.  Raises ValueError for a plan or shape the entries refuse."""
+    lib = _lib.load()
+    count, saved, ws = C.c_int32(), C.c_size_t(), C.c_size_t()
+    _lib.check(lib.gdb_cost_reg_train_layout(depth, cin, c, cout, B, D, H, W, None, 0, C.byref(count), C.byref(saved), C.byref(ws)))
+    regs = (_lib.GdbCostRegTrainRegion * count.value)()
+    _lib.check(lib.gdb_cost_reg_train_layout(depth, cin, c, cout, B, D, H, W, C.cast(regs, C.c_void_p), count.value, C.byref(count), None, None))
+    out = {}
+    for r in regs:
+        key = (int(r.buffer), r.name.decode())
+        if key in out:
+            raise _lib.GdbError(f"region {key} is listed twice")
+        out[key] = (int(r.offset), int(r.bytes), int(r.channels), int(r.level))
+    return out, saved.value, ws.value
+
+
+class _CostRegTrainFn(torch.autograd.Function):
+    """gdb_cost_reg_train / gdb_cost_reg_train_backward.  Inputs: the runner, the cost volume (no gradient is built for it) and the
+    parameters in `CostRegTrain.params()` order; the backward is not differentiable again."""
+
+    @staticmethod
+    def forward(ctx, runner, cost, *params):
+        lib = _lib.load()
+        B, _, D, H, W = cost.shape
+        dev = cost.device
+        regions, saved_bytes, ws_bytes = cost_reg_train_layout(runner.depth, runner.cin, runner.c, runner.cout, B, D, H, W)
+        saved = torch.empty((saved_bytes,), dtype=torch.uint8, device=dev)
+        volume = torch.empty((B, runner.cout, D, H, W), device=dev)
+        prob = torch.empty((B, D, H, W), device=dev)
+        stats = torch.empty((2 * sum(runner.channels),), device=dev)
+        ptrs = runner.param_pointers(params)
+        _lib.check(lib.gdb_cost_reg_train(runner.depth, runner.cin, runner.c, runner.cout, cost.data_ptr(), B, D, H, W, ptrs, runner.eps,
+                                          runner.momentum, saved.data_ptr(), saved_bytes, volume.data_ptr(), prob.data_ptr(),
+                                          stats.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        for t in runner.running_buffers():   # written in place by the library: whoever keys on versions (CostReg.pack) sees it
+            torch.autograd.graph.increment_version(t)
+        ctx.runner, ctx.ws_bytes, ctx.saved_bytes = runner, ws_bytes, saved_bytes
+        ctx.save_for_backward(cost, saved, *params)
+        if runner.keep:
+            runner.last = {"saved": saved, "regions": regions, "batch_stats": stats}
+        return volume, prob
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_volume, g_prob):
+        lib = _lib.load()
+        runner = ctx.runner
+        cost, saved, *params = ctx.saved_tensors
+        B, _, D, H, W = cost.shape
+        g_volume = None if g_volume is None else _c(g_volume, "g_volume")
+        g_prob = None if g_prob is None else _c(g_prob, "g_prob")
+        ws = torch.empty((ctx.ws_bytes,), dtype=torch.uint8, device=cost.device)
+        grads = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in params]
+        gptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        _lib.check(lib.gdb_cost_reg_train_backward(runner.depth, runner.cin, runner.c, runner.cout, cost.data_ptr(), B, D, H, W,
+                                                   runner.param_pointers(params), None if g_volume is None else g_volume.data_ptr(),
+                                                   None if g_prob is None else g_prob.data_ptr(), saved.data_ptr(), ctx.saved_bytes,
+                                                   ws.data_ptr(), ctx.ws_bytes, gptrs, torch.cuda.current_stream(cost.device).cuda_stream))
+        return (None, None, *grads)
+
+
+class CostRegTrain:
+    """Training-mode forward and backward of a `_UNet3d` on the HIP library: `CostRegTrain(module)(cost)` returns
+    (volume, prob) like `module.train()(cost)`, updates the module's running statistics in place on the device and carries a graph
+    to the module's parameters.  The cost volume gets no gradient: one that requires grad is refused.  Nothing falls back: a plan or
+    shape the library refuses raises ValueError.  With `keep` set, `last` holds the latest call's saved buffer, its regions and the
+    batch statistics (for inspection; off by default: it would pin the buffer until the next call)."""
+
+    def __init__(self, module: torch.nn.Module) -> None:
+        self.module = module
+        self.depth = int(module._depth)
+        self.cin, self.c = int(module.conv0[0].in_channels), int(module.conv0[0].out_channels)
+        self.cout = int(module.feat_head.out_channels)
+        self.blocks = [getattr(module, f"conv{i}") for i in range(3 * self.depth + 1)]
+        bns = [b[1] for b in self.blocks]
+        if any(bn.weight is None or bn.momentum is None for bn in bns):
+            raise ValueError("the train-mode HIP U-Net needs affine batch norms with a momentum")
+        eps, mom = {float(bn.eps) for bn in bns}, {float(bn.momentum) for bn in bns}
+        if len(eps) != 1 or len(mom) != 1:
+            raise ValueError(f"the U-Net's batch norms use different eps {sorted(eps)} or momentum {sorted(mom)}")
+        self.eps, self.momentum = eps.pop(), mom.pop()
+        self.channels = [int(b[0].out_channels) for b in self.blocks]
+        self.keep, self.last = False, None
+
+    def params(self):
+        ps = []
+        for b in self.blocks:
+            ps += [b[0].weight, b[1].weight, b[1].bias]
+        return ps + [self.module.feat_head.weight, self.module.prob_head.weight]
+
+    def running_buffers(self):
+        return [t for b in self.blocks for t in (b[1].running_mean, b[1].running_var, b[1].num_batches_tracked) if t is not None]
+
+    def param_pointers(self, params):
+        """The d_params array of include/gdb_nerf_hip.h from the parameters in `params()` order and the module's buffers."""
+        ptrs = []
+        for i, b in enumerate(self.blocks):
+            ptrs += [params[3 * i + k].data_ptr() for k in range(3)]
+            ptrs += [None if t is None else t.data_ptr() for t in (b[1].running_mean, b[1].running_var, b[1].num_batches_tracked)]
+        ptrs += [params[-2].data_ptr(), params[-1].data_ptr()]
+        return (C.c_void_p * len(ptrs))(*ptrs)
+
+    def __call__(self, cost: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if cost.requires_grad:
+            raise ValueError("CostRegTrain builds no gradient for the cost volume: pass one that does not require grad")
+        cost = _c(cost, "cost")
+        if cost.dim() != 5 or cost.shape[1] != self.cin:
+            raise ValueError(f"cost volume of shape {tuple(cost.shape)}, expected (B, {self.cin}, D, H, W)")
+        params = self.params()
+        for p in (*params, *self.running_buffers()):
+            if not p.is_cuda or p.device != cost.device or not p.is_contiguous() or (p.dtype != torch.float32 and p.dtype != torch.int64):
+                raise ValueError("CostRegTrain needs the module's parameters and buffers contiguous, fp32, on the cost volume's device")
+        return _CostRegTrainFn.apply(self, cost, *params)
+
+
 def _range_dims(search: torch.Tensor):
     if search.dim() == 2:   # (B, 2) near / far: broadcast over the target
         return 1, 1

@@ -197,6 +197,10 @@ class DepthNet(nn.Module):
         # the 3-D U-Nets on the HIP library (costvol.CostReg): eval mode and fp32 CUDA input only; off by default
         self.hip_cost_reg = bool(getattr(mvs, "hip_cost_reg", False))
         self._hip_regs = {}   # stage -> costvol.CostReg (not a module: no state-dict keys)
+        # mvs.hip_cost_reg_train (default false): in training mode fp32 CUDA tensors take the U-Nets' forward with batch statistics
+        # and their backward from the HIP library (costvol.CostRegTrain); eval mode, CPU tensors and other dtypes are untouched
+        self.hip_cost_reg_train = bool(getattr(mvs, "hip_cost_reg_train", False))
+        self._hip_regs_train = {}   # stage -> costvol.CostRegTrain
         # a whole stage as one library call (costvol.MvsStage): eval mode and fp32 CUDA inputs only; off by default
         self.hip_cascade = bool(getattr(mvs, "hip_cascade", False))
         # nerf.position_grad: the depth prior must carry a graph to the 3-D U-Nets.  Under that switch - and only while
@@ -277,7 +281,20 @@ class DepthNet(nn.Module):
             reg = self._hip_regs[s] = costvol.CostReg(self.cost_regs[s])
         return reg
 
+    def use_hip_cost_reg_train(self, feats) -> bool:
+        """The train-mode HIP U-Net (batch statistics + backward) needs its switch, training mode and fp32 CUDA tensors."""
+        return self.hip_cost_reg_train and self.training and _use_hip(feats, True)
+
+    def _hip_reg_train(self, s: int):
+        from ... import costvol
+        reg = self._hip_regs_train.get(s)
+        if reg is None or reg.module is not self.cost_regs[s]:
+            reg = self._hip_regs_train[s] = costvol.CostRegTrain(self.cost_regs[s])
+        return reg
+
     def _cost_reg(self, s: int, cost: torch.Tensor, feats: torch.Tensor):
+        if self.use_hip_cost_reg_train(feats):   # a shape the library refuses raises: nothing falls back
+            return self._hip_reg_train(s)(cost)
         if not self.use_hip_cost_reg(feats):
             return self.cost_regs[s](cost)
         return self._hip_reg(s)(cost)

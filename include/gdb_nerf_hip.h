@@ -852,6 +852,55 @@ int gdb_stage_nerf_backward(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim
                             int32_t S, const float* d_vox, const float* d_img, int64_t n_rays, const float* d_g_rgb_map, float* d_g_packed,
                             float* d_g_vox, float* d_g_img, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the cost-regularisation U-Nets in training mode: forward with batch statistics, and backward (ABI v7, added)
+ * _UNet3d.forward as the module computes it in .train(): every BatchNorm3d normalises with its batch's per-channel mean and biased
+ * variance over B*D*H*W, then ReLU; running_mean / running_var move by `momentum` (the unbiased variance for running_var) and
+ * num_batches_tracked grows by one, all on the device, in place.  The backward differentiates through the statistics.  Exact fp32 on
+ * v_mfma_f32_16x16x4_f32; statistics and every reduction are summed in double in a fixed order: no atomics, bit-identical runs.
+ * Accepted plans: those of gdb_cost_reg (depth 2 or 3, cin a multiple of 8 <= 256, base a multiple of 8 with base << depth <= 128,
+ * cout 1 .. 15: GDB_E_BADARG otherwise; D, H, W divisible by 2^depth: GDB_E_SHAPE otherwise), and one refusal more: a deepest level
+ * with a single value per channel (B * D*H*W >> 3 depth == 1) is GDB_E_SHAPE, as PyTorch refuses it.  Every refusal comes before the
+ * first launch.
+ *
+ * d_params (a HOST array of DEVICE pointers), for i = 0 .. 3 depth: conv{i}.0.weight, conv{i}.1.weight, conv{i}.1.bias,
+ *   conv{i}.1.running_mean, conv{i}.1.running_var, conv{i}.1.num_batches_tracked (int64) - six per layer, the last three may be NULL
+ *   (not updated) and are not read by the backward - then feat_head.weight and prob_head.weight: 6 (3 depth + 1) + 2 pointers, the
+ *   tensors in their own (PyTorch) layouts.  Weights are packed on the device; no parameter is copied to the host.
+ * d_grads (a HOST array of DEVICE pointers): conv{i}.0.weight, conv{i}.1.weight, conv{i}.1.bias gradients - three per layer - then
+ *   feat_head.weight's and prob_head.weight's: 3 (3 depth + 1) + 2 pointers, each in its tensor's own layout, overwritten.
+ *
+ * gdb_cost_reg_train_layout (host only, launches nothing): the named regions of the saved buffer (buffer 0) and of the backward's
+ *   workspace (buffer 1) and the two byte counts; out may be NULL to query *out_count.  Saved buffer, by name (BN layer i):
+ *     "conv{i}.z"       the raw convolution output, channel-last (B, D >> l, H >> l, W >> l, channels), l = level
+ *     "conv{i}.out"     relu(bn(z)), and for a transposed layer skip + relu(bn(z)): what the next layer reads
+ *     "conv{i}.mean", "conv{i}.invstd"   the batch mean and 1 / sqrt(biased variance + eps), `channels` floats each
+ *     "prob"            the softmax output; "packed", "heads.weight", "stat_partials": the forward's own scratch.
+ *   Workspace: "grad.l{l}" / "dz.l{l}" (the gradient of level l's activation and of the raw output being processed), "upstream"
+ *   (B, cout + 1, D, H, W), "packed_dx", "heads.weight_bwd", "heads.weight_grad", "bn_partials", "bn_means", and the weight gradient's
+ *   partials "dw_partials" (fp32, one per slab) and "dw_partials2" (double, one per 16 slabs).  Contents on entry do not matter.
+ * gdb_cost_reg_train: d_cost (B, cin, D, H, W) read in place -> d_volume (B, cout, D, H, W), d_prob (B, D, H, W), and d_batch_stats
+ *   (optional): per BN layer in order [mean | biased variance] x its channels.
+ * gdb_cost_reg_train_backward: d_g_volume / d_g_prob are the upstream of the two outputs (either may be NULL: zero); d_cost and
+ *   d_saved as the forward left them.  The gradient of d_cost is not built.  ReLU'(0) = 0.  A short buffer is GDB_E_WORKSPACE. */
+typedef struct GdbCostRegTrainRegion {
+    char name[32];
+    uint64_t offset;    /* bytes from the start of its buffer */
+    uint64_t bytes;
+    int32_t buffer;     /* 0: the saved buffer, 1: the backward's workspace */
+    int32_t channels;   /* 0 when the region is not per channel */
+    int32_t level;      /* resolution (D, H, W) >> level, -1 when the region is not a volume */
+    int32_t reserved;
+} GdbCostRegTrainRegion;
+int gdb_cost_reg_train_layout(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, int32_t B, int32_t D, int32_t H, int32_t W,
+                              GdbCostRegTrainRegion* out, int32_t capacity, int32_t* out_count, size_t* saved_bytes, size_t* ws_bytes);
+int gdb_cost_reg_train(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B, int32_t D,
+                       int32_t H, int32_t W, const void* const* d_params, float eps, float momentum, void* d_saved, size_t saved_bytes,
+                       float* d_volume, float* d_prob, float* d_batch_stats, void* stream);
+int gdb_cost_reg_train_backward(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B, int32_t D,
+                                int32_t H, int32_t W, const void* const* d_params, const float* d_g_volume, const float* d_g_prob,
+                                const void* d_saved, size_t saved_bytes, void* d_workspace, size_t ws_bytes, float* const* d_grads,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
