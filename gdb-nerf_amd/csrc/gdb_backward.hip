@@ -5,17 +5,8 @@
 // Derivative conventions: ReLU'(0) = 0 as torch; softplus with threshold 20 has derivative 1 above it;
 // var / mean are torch.var_mean with the unbiased divisor V - 1; both view softmaxes are over relu(score);
 // clamp_min(1e-6) on the weight sum has derivative 0 below 1e-6.
-#include "gdb_internal.h"
+#include "gdb_dw_tiles.h"
 #include <cstring>
-
-int gdb_fail(int code, const char* fmt, ...);
-int gdb_check_cfg(const GdbConfig* c);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
 
 // ============================================================================================
 // MLP backward
@@ -24,10 +15,11 @@ int gdb_check_cfg(const GdbConfig* c);
 //   1. the vector ALUs recompute the forward activations of the tile into LDS and run the per-sample chain of activation
 //      gradients, leaving for every linear layer its input X (rows = samples, or (view, sample) pairs) and the gradient dY of
 //      its pre-activation in LDS;
-//   2. the matrix cores add dW += dY^T X (v_mfma_f32_16x16x4_f32, K = the tile's rows) into accumulator registers that live
-//      across all tiles of the workgroup.  A bias gradient is the column of dY^T [X | 1].
-// After its last tile the workgroup writes ONE partial (the packed fp32 section's layout) to the workspace; k_mlp_bwd_reduce adds
-// the partials in workgroup order.  No atomics: the sum order is fixed by (grid, tile size) alone.
+//   2. the matrix cores add dW += dY^T [X | 1] into accumulator registers that live across all tiles of the workgroup, which writes
+//      ONE partial (the packed fp32 section's layout) to the workspace after its last tile; k_mlp_bwd_reduce adds the partials in
+//      workgroup order (gdb_dw_tiles.h).
+// The depth net's stage render (k_stage_nerf) walks the same chain with its linear layers on the matrix cores and its softmax backwards
+// in double; here both are fp32 on the vector ALUs - DESIGN.md 4.14 names the step not taken, and taking it changes this kernel's bits.
 #define BWD_TS 8
 #define BWD_THREADS 256
 #define BWD_MAX_WG 256
@@ -59,22 +51,12 @@ constexpr int L_END = L_SDH + BWD_TS * 64;
 static_assert(L_END * sizeof(float) <= 160 * 1024, "the tile does not fit the LDS of a CU");
 enum { ROW_SPRE = 0, ROW_A = 1, ROW_DS = 2, ROW_UPRE = 3, ROW_WV = 4, ROW_DU = 5, ROW_TMP = 6 };
 
-// ---- the products dW = dY^T [X | 1] as 16 x 16 output tiles ----
-struct BwdTile {
-    int dy, ldy, M, m0;      // dY in LDS: offset, row stride, columns in use, first column of this tile
-    int x, ldx, Nw, n0;      // X in LDS: offset of its first column, row stride, columns in use, first column of this tile
-    int xone;                // LDS offset of the ones column (column Nw of the product: the bias), -1 without bias
-    int perview;             // rows: V * BWD_TS, else BWD_TS
-    int w, ldw, b;           // packed section: offset of dW's element (0, 0) of this product, its row stride, bias offset (-1: none)
-};
+// ---- the products dW = dY^T [X | 1] ----
 #define BWD_TILES_PER_WAVE 19
-struct BwdTable { BwdTile t[4 * BWD_TILES_PER_WAVE]; int n; };
+typedef DwTable<4 * BWD_TILES_PER_WAVE> BwdTable;
 
 constexpr BwdTable bwd_make_table() {
-    BwdTable T{};
-    for (int i = 0; i < 4 * BWD_TILES_PER_WAVE; ++i) { T.t[i] = BwdTile{}; T.t[i].xone = -1; T.t[i].b = -1; }
-    int n = 0;
-    const int prods[11][11] = {
+    const DwProduct prods[11] = {
         // dy      ldy M   x            ldx Nw  xone         pv w                    ldw       b
         {L_VP,   20, GDB_CFR, L_FV + GDB_CFR, 24, 4,  L_FV + 23, 1, PW_VIEW_W,           4,        PW_VIEW_B},   // view_fc
         {L_DA,   32, GDB_GF,  L_GV,     20, GDB_CFR,  L_GV + 19, 1, PW_GLOB_W,           3 * GDB_CFR, PW_GLOB_B},   // global_fc, per-view columns
@@ -88,25 +70,11 @@ constexpr BwdTable bwd_make_table() {
         {L_ROW + ROW_DU, 8, 1, L_HID,   65, GDB_HID,  L_HID + 64, 1, PW_W2_W,            GDB_HID,  PW_W2_B},     // weight.2
         {L_FH,   8,  GDB_CV,  L_XH,     89, GDB_HID,  L_XH + 88, 0, PW_FH_W,             GDB_HID,  PW_FH_B},     // feat_head
     };
-    for (int p = 0; p < 11; ++p) {
-        const int* q = prods[p];
-        const int cols = q[5] + (q[6] >= 0 ? 1 : 0);
-        for (int m0 = 0; m0 < q[2]; m0 += 16)
-            for (int n0 = 0; n0 < cols; n0 += 16) {
-                if (n < 4 * BWD_TILES_PER_WAVE) T.t[n] = BwdTile{q[0], q[1], q[2], m0, q[3], q[4], q[5], n0, q[6], q[7], q[8], q[9], q[10]};
-                ++n;
-            }
-    }
-    T.n = n;
-    return T;
+    return dw_make_table<4 * BWD_TILES_PER_WAVE>(prods);
 }
 constexpr BwdTable k_bwd_table = bwd_make_table();
 static_assert(k_bwd_table.n <= 4 * BWD_TILES_PER_WAVE, "more output tiles than accumulators");
 __constant__ BwdTable c_bwd_table = k_bwd_table;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float relu_b(float x) { return x > 0.f ? x : 0.f; }
 
 // inner loops stay rolled: unrolled, their weight loads pile up in registers until the accumulators spill
 #define BWD_DOT _Pragma("unroll 4")
@@ -171,7 +139,7 @@ k_mlp_bwd(const float* __restrict__ pw, int V, int viewdir, int P, const float* 
                     a = fmaf(pw[PW_VIEW_W + 4 * c + 2], tl[GDB_CFR + 2], a);
                     a = fmaf(pw[PW_VIEW_W + 4 * c + 3], tl[GDB_CFR + 3], a);
                 }
-                g = tl[c] + relu_b(a);
+                g = tl[c] + relu_f(a);
             }
             lds[L_VP + r * 20 + c] = a;
             lds[L_GV + r * 20 + c] = g;
@@ -201,7 +169,7 @@ k_mlp_bwd(const float* __restrict__ pw, int V, int viewdir, int P, const float* 
                 for (int c = 0; c < 2 * GDB_CFR; ++c) a = fmaf(wr[GDB_CFR + c], lds[L_VM + s * 38 + c], a);
                 BWD_DOT
                 for (int c = 0; c < GDB_CFR; ++c) a = fmaf(wr[c], lds[L_GV + r * 20 + c], a);
-                val = relu_b(a);
+                val = relu_f(a);
             }
             lds[L_G + r * 33 + j] = val;
         }
@@ -215,12 +183,12 @@ k_mlp_bwd(const float* __restrict__ pw, int V, int viewdir, int P, const float* 
         }
         __syncthreads();
         BWD_FOR(s, TS) {
-            float m = relu_b(lds[L_ROW + s * 8 + ROW_SPRE]);
+            float m = relu_f(lds[L_ROW + s * 8 + ROW_SPRE]);
             BWD_VIEWS
-            for (int v = 1; v < V; ++v) m = fmaxf(m, relu_b(lds[L_ROW + (v * TS + s) * 8 + ROW_SPRE]));
+            for (int v = 1; v < V; ++v) m = fmaxf(m, relu_f(lds[L_ROW + (v * TS + s) * 8 + ROW_SPRE]));
             float sum = 0.f;
             BWD_VIEWS
-            for (int v = 0; v < V; ++v) { float e = expf(relu_b(lds[L_ROW + (v * TS + s) * 8 + ROW_SPRE]) - m); lds[L_ROW + (v * TS + s) * 8 + ROW_A] = e; sum += e; }
+            for (int v = 0; v < V; ++v) { float e = expf(relu_f(lds[L_ROW + (v * TS + s) * 8 + ROW_SPRE]) - m); lds[L_ROW + (v * TS + s) * 8 + ROW_A] = e; sum += e; }
             BWD_VIEWS
             for (int v = 0; v < V; ++v) lds[L_ROW + (v * TS + s) * 8 + ROW_A] /= sum;
         }
@@ -243,7 +211,7 @@ k_mlp_bwd(const float* __restrict__ pw, int V, int viewdir, int P, const float* 
             float a = pw[PW_FC_B + j];
             BWD_DOT
             for (int c = 0; c < GDB_GF; ++c) a = fmaf(pw[PW_FC_W + j * GDB_GF + c], lds[L_AGG + s * 33 + c], a);
-            lds[L_XH + s * 89 + GDB_HID + GDB_CV + j] = relu_b(a);
+            lds[L_XH + s * 89 + GDB_HID + GDB_CV + j] = relu_f(a);
         }
         __syncthreads();
         // ---- 7. x = relu(lr0 h)      :100-101
@@ -252,7 +220,7 @@ k_mlp_bwd(const float* __restrict__ pw, int V, int viewdir, int P, const float* 
             float a = pw[PW_LR0_B + j];
             BWD_DOT
             for (int c = 0; c < GDB_HD; ++c) a = fmaf(pw[PW_LR0_W + j * GDB_HD + c], lds[L_XH + s * 89 + GDB_HID + c], a);
-            lds[L_XH + s * 89 + j] = relu_b(a);
+            lds[L_XH + s * 89 + j] = relu_f(a);
         }
         __syncthreads();
         // ---- 8. heads on x: d sigma-pre (softplus, threshold 20), d feat_head-pre; the views' hidden rows of `weight`
@@ -281,7 +249,7 @@ k_mlp_bwd(const float* __restrict__ pw, int V, int viewdir, int P, const float* 
                 for (int c = 0; c < GDB_HID + GDB_HD; ++c) a = fmaf(wr[c], lds[L_XH + s * 89 + c], a);
                 BWD_DOT
                 for (int c = 0; c < GDB_FV; ++c) a = fmaf(wr[GDB_HID + GDB_HD + c], lds[L_FV + r * 24 + c], a);
-                val = relu_b(a);
+                val = relu_f(a);
             }
             lds[L_HID + r * 65 + j] = val;
         }
@@ -304,12 +272,12 @@ k_mlp_bwd(const float* __restrict__ pw, int V, int viewdir, int P, const float* 
         }
         __syncthreads();
         BWD_FOR(s, TS) {   // softmax over relu(u), its backward, and the ReLU of the score
-            float m = relu_b(lds[L_ROW + s * 8 + ROW_UPRE]);
+            float m = relu_f(lds[L_ROW + s * 8 + ROW_UPRE]);
             BWD_VIEWS
-            for (int v = 1; v < V; ++v) m = fmaxf(m, relu_b(lds[L_ROW + (v * TS + s) * 8 + ROW_UPRE]));
+            for (int v = 1; v < V; ++v) m = fmaxf(m, relu_f(lds[L_ROW + (v * TS + s) * 8 + ROW_UPRE]));
             float sum = 0.f;
             BWD_VIEWS
-            for (int v = 0; v < V; ++v) { float e = expf(relu_b(lds[L_ROW + (v * TS + s) * 8 + ROW_UPRE]) - m); lds[L_ROW + (v * TS + s) * 8 + ROW_WV] = e; sum += e; }
+            for (int v = 0; v < V; ++v) { float e = expf(relu_f(lds[L_ROW + (v * TS + s) * 8 + ROW_UPRE]) - m); lds[L_ROW + (v * TS + s) * 8 + ROW_WV] = e; sum += e; }
             float dot = 0.f;
             BWD_VIEWS
             for (int v = 0; v < V; ++v) {
@@ -471,28 +439,8 @@ k_mlp_bwd(const float* __restrict__ pw, int V, int viewdir, int P, const float* 
                 g_xin[((size_t)(r / TS) * n_alloc + i) * P + c] = a;
             }
         }
-        // ---- 20. dW += dY^T [X | 1] on the matrix cores: wave w owns output tiles w, w + 4, ...
-        {
-            const int li = lane & 15, kq = lane >> 4;
-#pragma unroll
-            for (int q = 0; q < BWD_TILES_PER_WAVE; ++q) {
-                const BwdTile& d = c_bwd_table.t[4 * q + wave];
-                const int rows = d.perview ? R : TS;
-                const int m = d.m0 + li, nn = d.n0 + li;
-                const bool mok = m < d.M;
-                const bool nok = nn < d.Nw || (nn == d.Nw && d.xone >= 0);
-                const int ao = d.dy + (mok ? m : 0);
-                const int bo = nn < d.Nw ? d.x + nn : (nok ? d.xone : d.x);
-                BWD_VIEWS
-                for (int k = 0; k < rows; k += 4) {
-                    float a = lds[ao + (k + kq) * d.ldy];
-                    float b = lds[bo + (k + kq) * d.ldx];
-                    a = mok ? a : 0.f;
-                    b = nok ? b : 0.f;
-                    acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[q], 0, 0, 0);
-                }
-            }
-        }
+        // ---- 20. dW += dY^T [X | 1] on the matrix cores
+        dw_accumulate<BWD_TILES_PER_WAVE>(c_bwd_table, lds, R, TS, acc, wave, lane);
         __syncthreads();   // the next tile overwrites the LDS image
     }
 
@@ -500,33 +448,11 @@ k_mlp_bwd(const float* __restrict__ pw, int V, int viewdir, int P, const float* 
     float* part = partials + (size_t)blockIdx.x * PW_FP32_FLOATS;
     BWD_FOR(k, PW_FP32_FLOATS) part[k] = 0.f;
     __syncthreads();
-    {
-        const int col = lane & 15, rq = lane >> 4;
-#pragma unroll
-        for (int q = 0; q < BWD_TILES_PER_WAVE; ++q) {
-            const BwdTile& d = c_bwd_table.t[4 * q + wave];
-            const int nn = d.n0 + col;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int m = d.m0 + 4 * rq + e;
-                if (m < d.M) {
-                    if (nn < d.Nw) part[d.w + m * d.ldw + nn] = acc[q][e];
-                    else if (nn == d.Nw && d.b >= 0) part[d.b + m] = acc[q][e];
-                }
-            }
-        }
-    }
+    dw_store_partial<BWD_TILES_PER_WAVE>(c_bwd_table, part, acc, wave, lane);
 }
 
-// Sum of the partials in workgroup order (fixed: bit-identical from run to run), accumulated in double.
 __global__ void k_mlp_bwd_reduce(const float* __restrict__ partials, int nparts, float* __restrict__ out) {
-    int o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= PW_FP32_FLOATS) return;
-    // a double accumulator: a small batch is one tile per workgroup, so this sum IS the sum over samples then, and a sequential fp32
-    // chain over a few hundred cancelling terms loses against the blocked sums of a CPU GEMM (seen on sigma.0.bias: 3 x the bound)
-    double s = 0.0;
-    for (int w = 0; w < nparts; ++w) s += (double)partials[(size_t)w * PW_FP32_FLOATS + o];
-    out[o] = (float)s;
+    dw_reduce(partials, nparts, PW_FP32_FLOATS, out);
 }
 
 static int bwd_grid(int64_t n_alloc) {
@@ -581,17 +507,6 @@ extern "C" int gdb_unpack_weight_grads(const GdbConfig* cfg, const float* h_pack
 // ============================================================================================
 // composite backward
 // ============================================================================================
-__global__ void k_seg_bounds_bwd(const int64_t* __restrict__ idx, const int64_t* __restrict__ total, int64_t n_alloc,
-                                 int64_t n_bundles, int32_t* __restrict__ seg) {   // as k_seg_bounds (gdb_mlp.hip)
-    int64_t n = total ? *total : n_alloc;
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || i >= n_alloc) return;
-    int64_t b = idx[i];
-    if (b < 0 || b >= n_bundles) return;
-    if (i == 0 || idx[i - 1] != b) seg[2 * b] = (int32_t)i;
-    if (i == n - 1 || idx[i + 1] != b) seg[2 * b + 1] = (int32_t)(i + 1);
-}
-
 // One lane per bundle.  alpha = 1 - e^-sigma, T_i = prod_{j<i}(1 - alpha_j), u_i = alpha_i T_i, D = max(sum u, 1e-6), w = u / D:
 //   g_u,i = (g_w,i - [sum u > 1e-6] sum_k g_w,k w_k) / D          g_sigma,i = g_u,i T_i (1 - alpha_i) - sum_{k>i} g_u,k u_k
 // Division-free in (1 - alpha), which underflows to 0 at sigma ~ 100.  The forward sweep parks T_{i+1} in g_sigma[i] (this lane's
@@ -636,11 +551,9 @@ extern "C" int gdb_render_weights_backward(const GdbConfig* cfg, const float* si
     if (n_alloc < 1 || n_bundles < 1 || n_alloc >= ((int64_t)1 << 31)) return gdb_fail(GDB_E_SHAPE, "bad sizes");
     hipStream_t st = (hipStream_t)stream_;
     int32_t* seg = (int32_t*)scratch;
-    hipError_t e = hipMemsetAsync(seg, 0, sizeof(int32_t) * 2 * (size_t)n_bundles, st);
-    if (e == hipSuccess) e = hipMemsetAsync(g_sigma, 0, sizeof(float) * (size_t)n_alloc, st);   // samples of no bundle, rows past *d_total
+    hipError_t e = hipMemsetAsync(g_sigma, 0, sizeof(float) * (size_t)n_alloc, st);   // samples of no bundle, rows past *d_total
     if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_seg_bounds_bwd, dim3((unsigned)((n_alloc + 255) / 256)), dim3(256), 0, st, idx, total, n_alloc, n_bundles, seg);
-    LAUNCH_CHECK("k_seg_bounds_bwd");
+    rc = gdb_seg_bounds_launch(idx, total, n_alloc, n_bundles, seg, st); if (rc) return rc;
     hipLaunchKernelGGL(k_render_weights_bwd, dim3((unsigned)((n_bundles + 255) / 256)), dim3(256), 0, st, n_bundles, (const int32_t*)seg,
                        sigma, g_weights, g_sigma);
     LAUNCH_CHECK("k_render_weights_bwd");

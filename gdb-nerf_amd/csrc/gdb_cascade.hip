@@ -18,19 +18,12 @@
 #include "gdb_internal.h"
 #include <cmath>
 
-int gdb_fail(int code, const char* fmt, ...);
 // gdb_costvol.hip / gdb_costreg.hip
 int gdb_costvol_pairs_(const float* d_src, float* d_pair_ws, size_t plane, size_t npairs, hipStream_t st);
 enum { CR_RUN_LOGITS = 0, CR_RUN_SOFTMAX = 1, CR_RUN_CHECK = 2 };
 int gdb_cost_reg_run_(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B, int32_t D,
                       int32_t H, int32_t W, const float* d_packed, void* d_ws, size_t ws_bytes, float* d_volume, float* d_prob,
                       int mode, void* stream_);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
 
 #include "gdb_costvol_body.h"
 

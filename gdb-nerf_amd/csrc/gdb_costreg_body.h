@@ -6,14 +6,6 @@
 #include <cmath>
 #include <cstring>
 
-int gdb_fail(int code, const char* fmt, ...);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 typedef float F2 __attribute__((ext_vector_type(2)));
 typedef float F4 __attribute__((ext_vector_type(4)));
 

@@ -7,14 +7,6 @@
 #include "gdb_internal.h"
 #include <cstdlib>
 
-int gdb_fail(int code, const char* fmt, ...);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 #include "gdb_costvol_body.h"
 
 __global__ void k_costvol_proj(int B, int V, const float* __restrict__ src_exts, const float* __restrict__ src_ints,

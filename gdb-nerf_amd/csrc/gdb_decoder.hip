@@ -31,9 +31,6 @@
 #include <cstring>
 #include <vector>
 
-int gdb_fail(int code, const char* fmt, ...);
-int gdb_check_cfg(const GdbConfig* c);
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float F2 __attribute__((ext_vector_type(2)));
 typedef float F4 __attribute__((ext_vector_type(4)));

@@ -27,8 +27,6 @@
 #include <cstring>
 #include <vector>
 
-int gdb_fail(int code, const char* fmt, ...);
-int gdb_check_cfg(const GdbConfig* c);
 // gdb_decoder.hip: k_se_gate on the per-segment channel sums (its own launch geometry)
 int gdb_dec_se_groups(int nseg);
 hipError_t gdb_dec_se_gate_launch(const float* part, int B, int nseg, float inv_hw, const float* w1, const float* w2, float* part2,

@@ -25,16 +25,6 @@
 // Compiled with -ffp-contract=off like gdb_ops.hip: the coordinates, levels and tap indices below are the forward's own bits.
 #include "gdb_internal.h"
 
-int gdb_fail(int code, const char* fmt, ...);
-int gdb_check_cfg(const GdbConfig* c);
-int gdb_check_frame(const GdbConfig* c, const GdbFrame* f, bool need_ptrs);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 #define EB_HDR_BYTES 256   // [0] uint32: max over the upstream of (float bits & 0x7fffffff)
 #define EB_ITEMS 64        // (view, sample) items per workgroup of k_encbwd_tex
 #define EB_THREADS 256
@@ -62,21 +52,6 @@ __device__ __forceinline__ int eb_exp(unsigned gb) {
 }
 __device__ __forceinline__ double eb_pow2(int k) { return __longlong_as_double((long long)(1023 + k) << 52); }   // -1022 <= k <= 1023
 
-__device__ __forceinline__ int eb_batch_of(int B, const int64_t* __restrict__ per_batch, int64_t i) {   // batch_of of gdb_ops.hip
-    int64_t acc = 0;
-    for (int bi = 0; bi < B; ++bi) { acc += per_batch[bi]; if (i < acc) return bi; }
-    return B - 1;
-}
-__device__ __forceinline__ int64_t eb_total(const int64_t* __restrict__ total, int64_t n_alloc) {
-    int64_t n = *total;
-    return n < 0 ? 0 : (n > n_alloc ? n_alloc : n);
-}
-// level geometry by selects: a per-lane index into the kernel-argument arrays would park them in private memory
-__device__ __forceinline__ void eb_level(const DevFrame& f, int l, int& W, int& H, unsigned& off) {
-    W = l == 0 ? f.lvlW[0] : (l == 1 ? f.lvlW[1] : (l == 2 ? f.lvlW[2] : f.lvlW[3]));
-    H = l == 0 ? f.lvlH[0] : (l == 1 ? f.lvlH[1] : (l == 2 ? f.lvlH[2] : f.lvlH[3]));
-    off = l == 0 ? f.lvlOff[0] : (l == 1 ? f.lvlOff[1] : (l == 2 ? f.lvlOff[2] : f.lvlOff[3]));
-}
 __device__ __forceinline__ void eb_add(long long* p, double c) {
     __hip_atomic_fetch_add(p, llrint(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // result unused: a no-return vector atomic
 }
@@ -86,7 +61,7 @@ __device__ __forceinline__ void eb_add(long long* p, double c) {
 // blockIdx.y = V: the flat g_vox
 __global__ void k_encbwd_max(int V, int P, int col0, const float* __restrict__ g_rfd, const float* __restrict__ g_vox,
                              const int64_t* __restrict__ total, int64_t n_alloc, unsigned* __restrict__ hdr) {
-    const int64_t n = eb_total(total, n_alloc);
+    const int64_t n = total_clamped(total, n_alloc);
     const int64_t step = (int64_t)gridDim.x * blockDim.x;
     unsigned m = 0;
     if ((int)blockIdx.y == V) {
@@ -120,9 +95,9 @@ __global__ void k_encbwd_vol(DevFrame f, const float* __restrict__ uvd, const in
     if (gb == 0 || gb >= 0x7f800000u) return;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t i = t >> 6;
-    if (i >= eb_total(total, n_alloc)) return;
+    if (i >= total_clamped(total, n_alloc)) return;
     const int r = (int)(t & 63), c = r & 7, dx = (r >> 3) & 1, dy = (r >> 4) & 1, dz = (r >> 5) & 1;
-    const int bi = eb_batch_of(f.B, per_batch, i);
+    const int bi = batch_of(f.B, per_batch, i);
     // k_encode_vox's coordinates
     float x = gs_coord(uvd[i * 3 + 0], f.W), y = gs_coord(uvd[i * 3 + 1], f.H), z = gs_coord(uvd[i * 3 + 2], f.D);
     float xf = floorf(x), yf = floorf(y), zf = floorf(z);
@@ -150,14 +125,14 @@ k_encbwd_tex(DevFrame f, const float* __restrict__ rays_xyz, const float* __rest
     __shared__ int s_bi[EB_ITEMS];
     const unsigned gb = hdr[0];
     if (gb == 0 || gb >= 0x7f800000u) return;   // uniform: the whole workgroup leaves
-    const int64_t n = eb_total(total, n_alloc);
+    const int64_t n = total_clamped(total, n_alloc);
     const int64_t i0 = (int64_t)blockIdx.x * EB_ITEMS;
     if (i0 >= n) return;
     const int v = blockIdx.y, tid = threadIdx.x;
     if (tid < EB_ITEMS) {
         const int64_t i = i0 + tid;
         if (i < n) {
-            const int bi = eb_batch_of(f.B, per_batch, i);
+            const int bi = batch_of(f.B, per_batch, i);
             const float* sc = src_cam(f, bi, v);
             float cc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -186,7 +161,7 @@ k_encbwd_tex(DevFrame f, const float* __restrict__ rays_xyz, const float* __rest
                 const double wl = k ? (double)frac : 1.0 - (double)frac;
                 const bool on = k == 0 || frac > 0.f;   // the forward skips level l1 when frac == 0
                 int W, H; unsigned off;
-                eb_level(f, l, W, H, off);
+                level_geom(f, l, W, H, off);
                 int x0, x1, y0, y1; float fx, fy;
                 tex_coord(tu, W, x0, x1, fx);
                 tex_coord(tv, H, y0, y1, fy);

@@ -22,15 +22,11 @@
 #include <type_traits>
 #include <cstring>
 
-int gdb_fail(int code, const char* fmt, ...);
-int gdb_check_cfg(const GdbConfig* c);
-int gdb_check_frame(const GdbConfig* c, const GdbFrame* f, bool need_ptrs);
 int gdb_build_dense_plan(const GdbConfig* cfg, const GdbFrame* f, void* ws, hipStream_t st);
 int gdb_build_pyr16(const GdbConfig* cfg, const GdbFrame* f, void* ws, hipStream_t st);
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- MFMA section of the packed weights ---------------------------------------------------------
 // 33 A-operand fragments (64 lanes x 8 halfs = 256 floats each), then fp32 tables.

@@ -5,6 +5,20 @@
 #include <stddef.h>
 #include "../../include/gdb_nerf_hip.h"
 
+// ---- error plumbing and argument checks (defined in gdb_ops.hip) ----------------------------
+int gdb_fail(int code, const char* fmt, ...);   // records the message for gdb_last_error, returns code
+int gdb_check_cfg(const GdbConfig* c);
+int gdb_check_frame(const GdbConfig* c, const GdbFrame* f, bool need_ptrs);
+
+#define LAUNCH_CHECK(name)                                                                    \
+    do {                                                                                      \
+        hipError_t e_ = hipGetLastError();                                                    \
+        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
+    } while (0)
+
+// Segment bounds [start, end) of every bundle in the bundle-major sample list (k_seg_bounds, gdb_mlp.hip): zeroes seg, then launches.
+int gdb_seg_bounds_launch(const int64_t* idx, const int64_t* total, int64_t n_alloc, int64_t n_bundles, int32_t* seg, hipStream_t st);
+
 // ---- fixed network sizes (every config of the reference: dtu_pretrain.yaml:17-42) ----------
 #define GDB_CF 16            // fpn.feat_dims[feat_level]
 #define GDB_CFR (GDB_CF + 3) // feature ⊕ rgb channels of img_feat
@@ -226,6 +240,28 @@ static inline DevFrame dev_frame(const GdbConfig& c, const GdbFrame& f, const Ws
 
 #ifdef __HIPCC__
 // ---- device helpers -----------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float relu_f(float x) { return x > 0.f ? x : 0.f; }
+
+// Batch item of compacted sample i, from the per-batch counts (bundle_sampler.py:318-319,370).
+__device__ __forceinline__ int batch_of(int B, const int64_t* __restrict__ per_batch, int64_t i) {
+    int64_t acc = 0;
+    for (int bi = 0; bi < B; ++bi) { acc += per_batch[bi]; if (i < acc) return bi; }
+    return B - 1;
+}
+// *total clamped to the rows the buffers hold
+__device__ __forceinline__ int64_t total_clamped(const int64_t* __restrict__ total, int64_t n_alloc) {
+    int64_t n = *total;
+    return n < 0 ? 0 : (n > n_alloc ? n_alloc : n);
+}
+// level geometry by selects: a per-lane index into the kernel-argument arrays would park them in private memory
+__device__ __forceinline__ void level_geom(const DevFrame& f, int l, int& W, int& H, unsigned& off) {
+    W = l == 0 ? f.lvlW[0] : (l == 1 ? f.lvlW[1] : (l == 2 ? f.lvlW[2] : f.lvlW[3]));
+    H = l == 0 ? f.lvlH[0] : (l == 1 ? f.lvlH[1] : (l == 2 ? f.lvlH[2] : f.lvlH[3]));
+    off = l == 0 ? f.lvlOff[0] : (l == 1 ? f.lvlOff[1] : (l == 2 ? f.lvlOff[2] : f.lvlOff[3]));
+}
+
 __device__ __forceinline__ const float* tar_cam(const DevFrame& f, int bi) {
     return f.cams + (size_t)bi * (TAR_STRIDE + f.V * SRC_STRIDE);
 }

@@ -23,14 +23,6 @@
 
 #include <math.h>
 
-int gdb_fail(int code, const char* fmt, ...);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 #define LS_THREADS 256
 #define LS_T 32        // output tile edge
 #define LS_WIN 7

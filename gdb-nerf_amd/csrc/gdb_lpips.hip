@@ -39,14 +39,6 @@
 #include <cstdio>
 #include <cstring>
 
-int gdb_fail(int code, const char* fmt, ...);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 typedef float F4 __attribute__((ext_vector_type(4)));
 
 #define LP_NCONV 13

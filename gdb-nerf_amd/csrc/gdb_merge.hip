@@ -4,10 +4,6 @@
 // HBM-bound: per bundle reads 4 (3 b^2 [+ 3 b^2 rgb_c] + ~2) and writes 4 (3 b^2 + 2 b^2) bytes.  Exact fp32, operation order of the reference's torch ops (-ffp-contract=off).
 #include "gdb_internal.h"
 
-int gdb_fail(int code, const char* fmt, ...);
-int gdb_check_cfg(const GdbConfig* c);
-int gdb_check_frame(const GdbConfig* c, const GdbFrame* f, bool need_ptrs);
-
 struct MergeArgs {
     int B, H, W, b, Q, rew;
     int ld, ms;  // floats between consecutive bundle rows of bf; between consecutive entries of the depth / opacity maps

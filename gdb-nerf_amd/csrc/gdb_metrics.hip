@@ -17,14 +17,6 @@
 //   read has been written in the same call, so the workspace's previous contents never matter.
 #include "gdb_internal.h"
 
-int gdb_fail(int code, const char* fmt, ...);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 #define EV_THREADS 256
 #define EV_TW 32
 #define EV_TH 16

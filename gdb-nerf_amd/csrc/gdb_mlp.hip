@@ -5,16 +5,8 @@
 #include "gdb_internal.h"
 #include <cstring>
 
-int gdb_fail(int code, const char* fmt, ...);
-int gdb_check_cfg(const GdbConfig* c);
 size_t gdb_mfma_section_floats();
 void gdb_pack_mfma_section(const float* fp32_section, float* out);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
 
 // ============================================================================================
 // weight packing (host)
@@ -252,6 +244,7 @@ extern "C" int gdb_mlp(const GdbConfig* cfg, const float* pw, int32_t V, const f
 __global__ void k_seg_bounds(const int64_t* __restrict__ idx, const int64_t* __restrict__ total, int64_t n_alloc,
                              int64_t n_bundles, int32_t* __restrict__ seg) {
     int64_t n = total ? *total : n_alloc;
+    if (n > n_alloc) n = n_alloc;   // a count past the buffers reads nothing past them: neither idx[i] nor idx[i + 1] below
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     int64_t b = idx[i];
@@ -306,10 +299,7 @@ extern "C" int gdb_composite(const GdbConfig* cfg, const float* sigma, const flo
     if (n_alloc >= ((int64_t)1 << 31)) return gdb_fail(GDB_E_SHAPE, "more than 2^31 samples");
     hipStream_t st = (hipStream_t)stream_;
     int32_t* seg = (int32_t*)scratch;
-    hipError_t e = hipMemsetAsync(seg, 0, sizeof(int32_t) * 2 * (size_t)n_bundles, st);
-    if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_seg_bounds, dim3((unsigned)((n_alloc + 255) / 256)), dim3(256), 0, st, idx, total, n_alloc, n_bundles, seg);
-    LAUNCH_CHECK("k_seg_bounds");
+    rc = gdb_seg_bounds_launch(idx, total, n_alloc, n_bundles, seg, st); if (rc) return rc;
     hipLaunchKernelGGL(k_comp_weights, dim3((unsigned)((n_bundles + 255) / 256)), dim3(256), 0, st, n_bundles, seg, sigma, weights);
     LAUNCH_CHECK("k_comp_weights");
     int64_t nt = n_bundles * (channels + 2);
@@ -319,7 +309,7 @@ extern "C" int gdb_composite(const GdbConfig* cfg, const float* sigma, const flo
     return GDB_OK;
 }
 
-static int seg_bounds(const int64_t* idx, const int64_t* total, int64_t n_alloc, int64_t n_bundles, int32_t* seg, hipStream_t st) {
+int gdb_seg_bounds_launch(const int64_t* idx, const int64_t* total, int64_t n_alloc, int64_t n_bundles, int32_t* seg, hipStream_t st) {
     hipError_t e = hipMemsetAsync(seg, 0, sizeof(int32_t) * 2 * (size_t)n_bundles, st);
     if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(k_seg_bounds, dim3((unsigned)((n_alloc + 255) / 256)), dim3(256), 0, st, idx, total, n_alloc, n_bundles, seg);
@@ -333,7 +323,7 @@ extern "C" int gdb_render_weights(const GdbConfig* cfg, const float* sigma, cons
     if (!sigma || !idx || !weights || !scratch) return gdb_fail(GDB_E_BADARG, "NULL pointer");
     if (n_alloc < 1 || n_bundles < 1 || n_alloc >= ((int64_t)1 << 31)) return gdb_fail(GDB_E_SHAPE, "bad sizes");
     hipStream_t st = (hipStream_t)stream_;
-    rc = seg_bounds(idx, total, n_alloc, n_bundles, (int32_t*)scratch, st); if (rc) return rc;
+    rc = gdb_seg_bounds_launch(idx, total, n_alloc, n_bundles, (int32_t*)scratch, st); if (rc) return rc;
     hipLaunchKernelGGL(k_comp_weights, dim3((unsigned)((n_bundles + 255) / 256)), dim3(256), 0, st, n_bundles, (const int32_t*)scratch, sigma, weights);
     LAUNCH_CHECK("k_comp_weights");
     return GDB_OK;
@@ -346,7 +336,7 @@ extern "C" int gdb_accumulate(const GdbConfig* cfg, const float* weights, const 
     if (!weights || !feat || !z || !idx || !fm || !dm || !om || !scratch) return gdb_fail(GDB_E_BADARG, "NULL pointer");
     if (n_alloc < 1 || n_bundles < 1 || channels < 1 || n_alloc >= ((int64_t)1 << 31)) return gdb_fail(GDB_E_SHAPE, "bad sizes");
     hipStream_t st = (hipStream_t)stream_;
-    rc = seg_bounds(idx, total, n_alloc, n_bundles, (int32_t*)scratch, st); if (rc) return rc;
+    rc = gdb_seg_bounds_launch(idx, total, n_alloc, n_bundles, (int32_t*)scratch, st); if (rc) return rc;
     int64_t nt = n_bundles * (channels + 2);
     hipLaunchKernelGGL(k_comp_accum, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, n_bundles, channels, 0,
                        (const int32_t*)scratch, weights, feat, z, fm, dm, om);

@@ -31,12 +31,6 @@ int gdb_fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 extern "C" int gdb_abi_version(void) { return GDB_ABI_VERSION; }
 extern "C" const char* gdb_last_error(void) { return g_err; }
 
@@ -953,13 +947,6 @@ extern "C" int gdb_sample(const GdbConfig* cfg, const GdbFrame* f, void* ws, flo
 // ============================================================================================
 // A4  encode
 // ============================================================================================
-// Batch item of compacted sample i, from the per-batch counts (bundle_sampler.py:318-319,370).
-__device__ __forceinline__ int batch_of(int B, const int64_t* __restrict__ per_batch, int64_t i) {
-    int64_t acc = 0;
-    for (int bi = 0; bi < B; ++bi) { acc += per_batch[bi]; if (i < acc) return bi; }
-    return B - 1;
-}
-
 // Voxel feature: 5-D grid_sample, trilinear / border / align_corners=False.  :322-324
 // One thread per (sample, channel): consecutive samples sit on consecutive bundles, so the
 // NCDHW volume is read along x.

@@ -25,33 +25,8 @@
 //                    order; the sample offsets come from an exclusive scan of the counts, as in gdb_sample)
 #include "gdb_internal.h"
 
-int gdb_fail(int code, const char* fmt, ...);
-int gdb_check_cfg(const GdbConfig* c);
-int gdb_check_frame(const GdbConfig* c, const GdbFrame* f, bool need_ptrs);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
 #define PB_THREADS 128
 
-__device__ __forceinline__ int pb_batch_of(int B, const int64_t* __restrict__ per_batch, int64_t i) {   // batch_of of gdb_ops.hip
-    int64_t acc = 0;
-    for (int bi = 0; bi < B; ++bi) { acc += per_batch[bi]; if (i < acc) return bi; }
-    return B - 1;
-}
-__device__ __forceinline__ int64_t pb_total(const int64_t* __restrict__ total, int64_t n_alloc) {
-    int64_t n = *total;
-    return n < 0 ? 0 : (n > n_alloc ? n_alloc : n);
-}
-// level geometry by selects: a per-lane index into the kernel-argument arrays would park them in private memory
-__device__ __forceinline__ void pb_level(const DevFrame& f, int l, int& W, int& H, unsigned& off) {
-    W = l == 0 ? f.lvlW[0] : (l == 1 ? f.lvlW[1] : (l == 2 ? f.lvlW[2] : f.lvlW[3]));
-    H = l == 0 ? f.lvlH[0] : (l == 1 ? f.lvlH[1] : (l == 2 ? f.lvlH[2] : f.lvlH[3]));
-    off = l == 0 ? f.lvlOff[0] : (l == 1 ? f.lvlOff[1] : (l == 2 ? f.lvlOff[2] : f.lvlOff[3]));
-}
 // the unclamped coordinate of gs_coord (same expression, same bits): strictly inside (0, size - 1) the clamp passes the derivative
 __device__ __forceinline__ bool gs_inside(float g, int size) {
     float x = ((g + 1.f) * (float)size - 1.f) / 2.f;
@@ -79,8 +54,8 @@ k_posbwd_vol(DevFrame f, const float* __restrict__ uvd, const int64_t* __restric
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_alloc) return;
     float gd = 0.f;
-    if (i < pb_total(total, n_alloc)) {
-        const int bi = pb_batch_of(f.B, per_batch, i);
+    if (i < total_clamped(total, n_alloc)) {
+        const int bi = batch_of(f.B, per_batch, i);
         // k_encode_vox's coordinates
         const float dn = uvd[i * 3 + 2];
         float x = gs_coord(uvd[i * 3 + 0], f.W), y = gs_coord(uvd[i * 3 + 1], f.H), z = gs_coord(dn, f.D);
@@ -120,7 +95,7 @@ k_posbwd_vol(DevFrame f, const float* __restrict__ uvd, const int64_t* __restric
 __device__ __forceinline__ void pb_tex_level(const DevFrame& f, const float* __restrict__ pyr, int l, float u, float v,
                                              const float g[GDB_CP], double& val, double& du, double& dv) {
     int W, H; unsigned off;
-    pb_level(f, l, W, H, off);
+    level_geom(f, l, W, H, off);
     int x0, x1, y0, y1; float fx, fy;
     tex_coord(u, W, x0, x1, fx);
     tex_coord(v, H, y0, y1, fy);
@@ -156,8 +131,8 @@ k_posbwd_centre(DevFrame f, const float* __restrict__ rays_xyz, const float* __r
     if (i >= n_alloc) return;
     double gw[3] = {0.0, 0.0, 0.0};   // gradient with respect to every sub-ray point, summed over the centre paths and the views
     double gb = 0.0;
-    if (i < pb_total(total, n_alloc)) {
-        const int bi = pb_batch_of(f.B, per_batch, i);
+    if (i < total_clamped(total, n_alloc)) {
+        const int bi = batch_of(f.B, per_batch, i);
         const float* tc = tar_cam(f, bi);
         const float ball = ball_radii[i];
         for (int v = 0; v < f.V; ++v) {
@@ -280,8 +255,8 @@ k_posbwd_colour(DevFrame f, const float* __restrict__ rays_xyz, const int64_t* _
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t i = t / BB;
     const int s = (int)(t - i * BB);
-    if (i >= pb_total(total, n_alloc)) return;   // (the tail rows were zeroed by k_posbwd_centre)
-    const int bi = pb_batch_of(f.B, per_batch, i);
+    if (i >= total_clamped(total, n_alloc)) return;   // (the tail rows were zeroed by k_posbwd_centre)
+    const int bi = batch_of(f.B, per_batch, i);
     float p[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) p[c] = rays_xyz[((size_t)i * 3 + c) * BB + s];
@@ -384,7 +359,7 @@ k_smpbwd(DevFrame f, const int32_t* __restrict__ spb, const int32_t* __restrict_
     const int cnt = min(max(spb[t], 0), f.S_max);   // the counts are data: ceil / clamp have derivative 0
     q.count = cnt;
     const int64_t off = (int64_t)offs[t] + bsum[t / SCAN_BLOCK];
-    const int64_t n = pb_total(total, n_alloc);
+    const int64_t n = total_clamped(total, n_alloc);
     double md[3] = {0.0, 0.0, 0.0};
 #pragma unroll
     for (int s = 0; s < BB; ++s)

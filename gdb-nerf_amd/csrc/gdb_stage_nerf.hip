@@ -16,24 +16,15 @@
 //
 // Derivative conventions (shared with k_mlp_bwd): ReLU'(0) = 0; softplus has threshold 20; the variance divisor is
 // V - 1; both view softmaxes are over relu(score); the colour channels feed the blend AND the layers, their gradient is the sum.
-#include "gdb_internal.h"
+#include "gdb_dw_tiles.h"
 #include <cstring>
-
-int gdb_fail(int code, const char* fmt, ...);
-
-#define LAUNCH_CHECK(name)                                                                    \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) return gdb_fail(GDB_E_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
+#include <type_traits>
 
 #define SN_THREADS 256
 #define SN_MAX_WG 256
 #define SN_RM 64     // (view, sample) rows of a tile at most
 #define SN_SM 16     // samples of a tile at most
 #define SN_XW (GDB_HID + GDB_HD)   // 88: [x | vox | im], the shared columns of color.0
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- packed weights (float offsets; every block 4-float aligned), C = feat_dim + 3 ----
 template <int C> struct SnW {
@@ -87,23 +78,13 @@ static_assert(SnL<35>::END * sizeof(float) <= 160 * 1024, "the tile does not fit
 enum { ROW_SPRE = 0, ROW_A = 1, ROW_DS = 2, ROW_UPRE = 3, ROW_WV = 4, ROW_DU = 5, ROW_TMP = 6 };
 enum { SMP_SIGMA = 0, SMP_SPRE = 1, SMP_RGB = 2 /* 3 */, SMP_W = 5, SMP_T = 6, SMP_E = 7, SMP_GRGB = 8 /* 3 */ };
 
-// ---- the products dW = dY^T [X | 1] as 16 x 16 output tiles (as gdb_backward.hip) ----
-struct SnTile {
-    int dy, ldy, M, m0;
-    int x, ldx, Nw, n0;
-    int xone;
-    int perview;
-    int w, ldw, b;
-};
+// ---- the products dW = dY^T [X | 1] ----
 #define SN_MAX_TILES 80
-struct SnTable { SnTile t[SN_MAX_TILES]; int n; };
+typedef DwTable<SN_MAX_TILES> SnTable;
 
 template <int C> constexpr SnTable sn_make_table() {
     using L = SnL<C>; using W = SnW<C>;
-    SnTable T{};
-    for (int i = 0; i < SN_MAX_TILES; ++i) { T.t[i] = SnTile{}; T.t[i].xone = -1; T.t[i].b = -1; }
-    int n = 0;
-    const int prods[10][11] = {
+    const DwProduct prods[10] = {
         // dy               ldy M        x           ldx    Nw      xone          pv w                 ldw      b
         {L::VP,             C,  C,       L::XT + C,  C + 5, 4,      L::XT + C + 4, 1, W::VIEW_W,        4,       W::VIEW_B},   // view_fc
         {L::DA,             32, GDB_GF,  L::GV,      C + 1, C,      L::GV + C,    1, W::GLOB_W,        3 * C,   W::GLOB_B},   // global_fc, per-view columns
@@ -116,28 +97,11 @@ template <int C> constexpr SnTable sn_make_table() {
         {L::DHID,           64, GDB_HID, L::XT,      C + 5, C + 4,  L::XT + C + 4, 1, W::C0_W + SN_XW, W::W0IN, W::C0_B},     // color.0, per-view tail
         {L::ROW + ROW_DU,   8,  1,       L::HID,     65,    GDB_HID, L::HID + 64, 1, W::C2_W,          GDB_HID, W::C2_B},     // color.2
     };
-    for (int p = 0; p < 10; ++p) {
-        const int* q = prods[p];
-        const int cols = q[5] + (q[6] >= 0 ? 1 : 0);
-        for (int m0 = 0; m0 < q[2]; m0 += 16)
-            for (int n0 = 0; n0 < cols; n0 += 16) {
-                if (n < SN_MAX_TILES) T.t[n] = SnTile{q[0], q[1], q[2], m0, q[3], q[4], q[5], n0, q[6], q[7], q[8], q[9], q[10]};
-                ++n;
-            }
-    }
-    T.n = n;
-    return T;
+    return dw_make_table<SN_MAX_TILES>(prods);
 }
 template <int C> struct SnTab { static constexpr SnTable host = sn_make_table<C>(); static constexpr int per_wave = (host.n + 3) / 4; };
 static_assert(SnTab<35>::host.n <= SN_MAX_TILES && SnTab<19>::host.n <= SN_MAX_TILES && SnTab<11>::host.n <= SN_MAX_TILES, "more output tiles than table slots");
-__constant__ SnTable c_sn_table_11 = SnTab<11>::host;
-__constant__ SnTable c_sn_table_19 = SnTab<19>::host;
-__constant__ SnTable c_sn_table_35 = SnTab<35>::host;
-template <int C> __device__ __forceinline__ const SnTable& sn_table() {
-    if constexpr (C == 11) return c_sn_table_11; else if constexpr (C == 19) return c_sn_table_19; else return c_sn_table_35;
-}
-
-__device__ __forceinline__ float relu_s(float x) { return x > 0.f ? x : 0.f; }
+template <int C> __constant__ SnTable c_sn_table = SnTab<C>::host;
 
 #define SN_DOT _Pragma("unroll 4")
 #define SN_VIEWS _Pragma("nounroll")
@@ -147,6 +111,7 @@ __device__ __forceinline__ float relu_s(float x) { return x > 0.f ? x : 0.f; }
 // LDS, the weights in global memory.  init = lds[init + (row % imod) * ldi + m] when init >= 0 (may be Y itself: every element is read
 // and written by the same lane), else bias[m] (or 0).  Forward layers: sm = row stride of W, sk = 1.  dX = dY W: sm = 1, sk = row stride.
 // Output tiles go round the four waves; A row i feeds D row i only, so rows past the tile's last hold whatever they hold.
+// (k_mlp_bwd has the same layers as fp32 dot products on the vector ALUs: another summation order, its own bits - not shared.)
 __device__ __forceinline__ void sn_gemm(float* __restrict__ lds, int y, int ldy, int x, int ldx, int K, int M, int rows16,
                                         const float* __restrict__ wm, int sm, int sk, const float* __restrict__ bias,
                                         int init, int ldi, int imod, bool relu, int wave, int lane) {
@@ -180,7 +145,7 @@ __device__ __forceinline__ void sn_gemm(float* __restrict__ lds, int y, int ldy,
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = r0 + 4 * kq + e;
-                lds[y + row * ldy + m] = relu ? relu_s(acc[e]) : acc[e];
+                lds[y + row * ldy + m] = relu ? relu_f(acc[e]) : acc[e];
             }
         }
     }
@@ -236,7 +201,7 @@ k_stage_nerf(const float* __restrict__ pw, int V, int S, int viewdir, int rpt, c
                     a = fmaf(pw[W::VIEW_W + 4 * c + 2], tl[C + 2], a);
                     a = fmaf(pw[W::VIEW_W + 4 * c + 3], tl[C + 3], a);
                 }
-                g = tl[c] + relu_s(a);
+                g = tl[c] + relu_f(a);
                 lds[L::VP + r * C + c] = a;
             }
             lds[L::GV + r * (C + 1) + c] = g;
@@ -273,12 +238,12 @@ k_stage_nerf(const float* __restrict__ pw, int V, int S, int viewdir, int rpt, c
         }
         __syncthreads();
         SN_FOR(s, TSP) {
-            float m = relu_s(lds[L::ROW + s * 8 + ROW_SPRE]);
+            float m = relu_f(lds[L::ROW + s * 8 + ROW_SPRE]);
             SN_VIEWS
-            for (int v = 1; v < V; ++v) m = fmaxf(m, relu_s(lds[L::ROW + (v * TSP + s) * 8 + ROW_SPRE]));
+            for (int v = 1; v < V; ++v) m = fmaxf(m, relu_f(lds[L::ROW + (v * TSP + s) * 8 + ROW_SPRE]));
             float sum = 0.f;
             SN_VIEWS
-            for (int v = 0; v < V; ++v) { float e = expf(relu_s(lds[L::ROW + (v * TSP + s) * 8 + ROW_SPRE]) - m); lds[L::ROW + (v * TSP + s) * 8 + ROW_A] = e; sum += e; }
+            for (int v = 0; v < V; ++v) { float e = expf(relu_f(lds[L::ROW + (v * TSP + s) * 8 + ROW_SPRE]) - m); lds[L::ROW + (v * TSP + s) * 8 + ROW_A] = e; sum += e; }
             SN_VIEWS
             for (int v = 0; v < V; ++v) lds[L::ROW + (v * TSP + s) * 8 + ROW_A] /= sum;
         }
@@ -325,12 +290,12 @@ k_stage_nerf(const float* __restrict__ pw, int V, int S, int viewdir, int rpt, c
         }
         __syncthreads();
         SN_FOR(s, TSP) {
-            float m = relu_s(lds[L::ROW + s * 8 + ROW_UPRE]);
+            float m = relu_f(lds[L::ROW + s * 8 + ROW_UPRE]);
             SN_VIEWS
-            for (int v = 1; v < V; ++v) m = fmaxf(m, relu_s(lds[L::ROW + (v * TSP + s) * 8 + ROW_UPRE]));
+            for (int v = 1; v < V; ++v) m = fmaxf(m, relu_f(lds[L::ROW + (v * TSP + s) * 8 + ROW_UPRE]));
             float sum = 0.f;
             SN_VIEWS
-            for (int v = 0; v < V; ++v) { float e = expf(relu_s(lds[L::ROW + (v * TSP + s) * 8 + ROW_UPRE]) - m); lds[L::ROW + (v * TSP + s) * 8 + ROW_WV] = e; sum += e; }
+            for (int v = 0; v < V; ++v) { float e = expf(relu_f(lds[L::ROW + (v * TSP + s) * 8 + ROW_UPRE]) - m); lds[L::ROW + (v * TSP + s) * 8 + ROW_WV] = e; sum += e; }
             float c0 = 0.f, c1 = 0.f, c2 = 0.f;
             SN_VIEWS
             for (int v = 0; v < V; ++v) {
@@ -455,7 +420,8 @@ k_stage_nerf(const float* __restrict__ pw, int V, int S, int viewdir, int rpt, c
             // ---- 16. d agg = fc^T dY
             sn_gemm(lds, L::DAGG, 32, L::DFC, 16, GDB_IM, GDB_GF, 16, pw + W::FC_W, 1, GDB_GF, nullptr, -1, 0, 1, false, wave, lane);
             __syncthreads();
-            // ---- 17. d a_v = d agg . G_v, the softmax's backward and the ReLU of the score
+            // ---- 17. d a_v = d agg . G_v, the softmax's backward and the ReLU of the score (in double as step 11, where k_mlp_bwd's
+            //          is fp32: not shared, either change moves bits)
             SN_FOR(r, R) {
                 int s = r % TSP;
                 float a = 0.f;
@@ -532,29 +498,8 @@ k_stage_nerf(const float* __restrict__ pw, int V, int S, int viewdir, int rpt, c
                     g_xin[((size_t)i * V + v) * P + c] = a;
                 }
             }
-            // ---- 23. dW += dY^T [X | 1] on the matrix cores: wave w owns output tiles w, w + 4, ...
-            {
-                const SnTable& tab = sn_table<C>();
-                const int li = lane & 15, kq = lane >> 4;
-#pragma unroll
-                for (int q = 0; q < PER_WAVE; ++q) {
-                    const SnTile& d = tab.t[4 * q + wave];
-                    const int rows = d.perview ? R : TSP;
-                    const int m = d.m0 + li, nn = d.n0 + li;
-                    const bool mok = m < d.M;
-                    const bool nok = nn < d.Nw || (nn == d.Nw && d.xone >= 0);
-                    const int ao = d.dy + (mok ? m : 0);
-                    const int bo = nn < d.Nw ? d.x + nn : (nok ? d.xone : d.x);
-                    SN_VIEWS
-                    for (int k = 0; k < rows; k += 4) {
-                        float a = lds[ao + (k + kq) * d.ldy];
-                        float b = lds[bo + (k + kq) * d.ldx];
-                        a = mok ? a : 0.f;
-                        b = nok ? b : 0.f;
-                        acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[q], 0, 0, 0);
-                    }
-                }
-            }
+            // ---- 23. dW += dY^T [X | 1] on the matrix cores
+            dw_accumulate<PER_WAVE>(c_sn_table<C>, lds, R, TSP, acc, wave, lane);
         }
         __syncthreads();   // the next tile overwrites the LDS image
     }
@@ -564,35 +509,22 @@ k_stage_nerf(const float* __restrict__ pw, int V, int S, int viewdir, int rpt, c
         float* part = partials + (size_t)blockIdx.x * W::FLOATS;
         SN_FOR(k, W::FLOATS) part[k] = 0.f;
         __syncthreads();
-        const SnTable& tab = sn_table<C>();
-        const int col = lane & 15, rq = lane >> 4;
-#pragma unroll
-        for (int q = 0; q < PER_WAVE; ++q) {
-            const SnTile& d = tab.t[4 * q + wave];
-            const int nn = d.n0 + col;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int m = d.m0 + 4 * rq + e;
-                if (m < d.M) {
-                    if (nn < d.Nw) part[d.w + m * d.ldw + nn] = acc[q][e];
-                    else if (nn == d.Nw && d.b >= 0) part[d.b + m] = acc[q][e];
-                }
-            }
-        }
+        dw_store_partial<PER_WAVE>(c_sn_table<C>, part, acc, wave, lane);
     }
 }
 
-// Sum of the partials in workgroup order (fixed: bit-identical from run to run), accumulated in double.
 __global__ void k_stage_reduce(const float* __restrict__ partials, int nparts, int floats, float* __restrict__ out) {
-    int o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= floats) return;
-    double s = 0.0;
-    for (int w = 0; w < nparts; ++w) s += (double)partials[(size_t)w * floats + o];
-    out[o] = (float)s;
+    dw_reduce(partials, nparts, floats, out);
 }
 
 // ---- host ----
-static int sn_floats(int C) { return C == 11 ? SnW<11>::FLOATS : (C == 19 ? SnW<19>::FLOATS : SnW<35>::FLOATS); }
+// f(std::integral_constant<int, C>) for the C = feat_dim + 3 of the three networks sn_check_net lets through
+template <class F> static auto sn_dispatch(int C, F&& f) {
+    if (C == 11) return f(std::integral_constant<int, 11>{});
+    if (C == 19) return f(std::integral_constant<int, 19>{});
+    return f(std::integral_constant<int, 35>{});
+}
+static int sn_floats(int C) { return sn_dispatch(C, [](auto c) { return SnW<decltype(c)::value>::FLOATS; }); }
 
 static int sn_check_net(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim, int32_t viewdir_agg) {
     if (feat_dim != 8 && feat_dim != 16 && feat_dim != 32) return gdb_fail(GDB_E_BADARG, "stage NeRF: feat_dim %d is not 8, 16 or 32", feat_dim);
@@ -629,16 +561,16 @@ extern "C" int gdb_stage_nerf_packed_floats(int32_t feat_dim, int32_t voxel_dim,
     return GDB_OK;
 }
 
-template <int C> static void sn_offsets(int offs[16], int sizes[16]) {
-    using W = SnW<C>;
-    const int o[16] = {W::VIEW_W, W::VIEW_B, W::GLOB_W, W::GLOB_B, W::AGG_W, W::AGG_B, W::FC_W, W::FC_B, W::LR0_W, W::LR0_B, W::SIG_W, W::SIG_B,
-                       W::C0_W, W::C0_B, W::C2_W, W::C2_B};
-    const int s[16] = {C * 4, C, GDB_GF * 3 * C, GDB_GF, GDB_GF, 1, GDB_IM * GDB_GF, GDB_IM, GDB_HID * GDB_HD, GDB_HID, GDB_HID, 1,
-                       GDB_HID * W::W0IN, GDB_HID, GDB_HID, 1};
-    for (int i = 0; i < 16; ++i) { offs[i] = o[i]; sizes[i] = s[i]; }
-}
-static void sn_offsets_of(int C, int offs[16], int sizes[16]) {
-    if (C == 11) sn_offsets<11>(offs, sizes); else if (C == 19) sn_offsets<19>(offs, sizes); else sn_offsets<35>(offs, sizes);
+static void sn_offsets_of(int C_, int offs[16], int sizes[16]) {
+    sn_dispatch(C_, [&](auto c) {
+        constexpr int C = decltype(c)::value;
+        using W = SnW<C>;
+        const int o[16] = {W::VIEW_W, W::VIEW_B, W::GLOB_W, W::GLOB_B, W::AGG_W, W::AGG_B, W::FC_W, W::FC_B, W::LR0_W, W::LR0_B, W::SIG_W, W::SIG_B,
+                           W::C0_W, W::C0_B, W::C2_W, W::C2_B};
+        const int s[16] = {C * 4, C, GDB_GF * 3 * C, GDB_GF, GDB_GF, 1, GDB_IM * GDB_GF, GDB_IM, GDB_HID * GDB_HD, GDB_HID, GDB_HID, 1,
+                           GDB_HID * W::W0IN, GDB_HID, GDB_HID, 1};
+        for (int i = 0; i < 16; ++i) { offs[i] = o[i]; sizes[i] = s[i]; }
+    });
 }
 
 extern "C" int gdb_pack_stage_nerf_weights(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim, int32_t viewdir_agg,
@@ -680,13 +612,6 @@ extern "C" int gdb_stage_nerf_layout(int32_t feat_dim, int32_t voxel_dim, int32_
     return GDB_OK;
 }
 
-template <int C, bool BWD>
-static void sn_launch(int g, hipStream_t st, const float* pw, int V, int S, int viewdir, int rpt, const float* vox, const float* xin, int64_t n_rays,
-                      float* rgb_map, float* sigma, float* rgb, const float* g_map, float* g_vox, float* g_xin, float* partials) {
-    hipLaunchKernelGGL((k_stage_nerf<C, BWD>), dim3((unsigned)g), dim3(SN_THREADS), 0, st, pw, V, S, viewdir, rpt, vox, xin, n_rays, rgb_map, sigma, rgb,
-                       g_map, g_vox, g_xin, partials);
-}
-
 extern "C" int gdb_stage_nerf(int32_t feat_dim, int32_t voxel_dim, int32_t hid_dim, int32_t viewdir_agg, const float* d_packed, int32_t V, int32_t S,
                               const float* d_vox, const float* d_img, int64_t n_rays, float* d_rgb_map, float* d_sigma, float* d_rgb, void* stream_) {
     size_t lay[3];
@@ -694,9 +619,10 @@ extern "C" int gdb_stage_nerf(int32_t feat_dim, int32_t voxel_dim, int32_t hid_d
     if (!d_packed || !d_vox || !d_img || !d_rgb_map) return gdb_fail(GDB_E_BADARG, "NULL pointer");
     hipStream_t st = (hipStream_t)stream_;
     const int g = (int)lay[1], rpt = (int)lay[2], C = feat_dim + 3;
-    if (C == 11) sn_launch<11, false>(g, st, d_packed, V, S, viewdir_agg, rpt, d_vox, d_img, n_rays, d_rgb_map, d_sigma, d_rgb, nullptr, nullptr, nullptr, nullptr);
-    else if (C == 19) sn_launch<19, false>(g, st, d_packed, V, S, viewdir_agg, rpt, d_vox, d_img, n_rays, d_rgb_map, d_sigma, d_rgb, nullptr, nullptr, nullptr, nullptr);
-    else sn_launch<35, false>(g, st, d_packed, V, S, viewdir_agg, rpt, d_vox, d_img, n_rays, d_rgb_map, d_sigma, d_rgb, nullptr, nullptr, nullptr, nullptr);
+    sn_dispatch(C, [&](auto c) {
+        hipLaunchKernelGGL((k_stage_nerf<decltype(c)::value, false>), dim3((unsigned)g), dim3(SN_THREADS), 0, st, d_packed, V, S, viewdir_agg, rpt, d_vox, d_img,
+                           n_rays, d_rgb_map, d_sigma, d_rgb, (const float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+    });
     LAUNCH_CHECK("k_stage_nerf");
     return GDB_OK;
 }
@@ -711,9 +637,10 @@ extern "C" int gdb_stage_nerf_backward(int32_t feat_dim, int32_t voxel_dim, int3
     hipStream_t st = (hipStream_t)stream_;
     const int g = (int)lay[1], rpt = (int)lay[2], C = feat_dim + 3;
     float* parts = (float*)d_workspace;
-    if (C == 11) sn_launch<11, true>(g, st, d_packed, V, S, viewdir_agg, rpt, d_vox, d_img, n_rays, nullptr, nullptr, nullptr, d_g_rgb_map, d_g_vox, d_g_img, parts);
-    else if (C == 19) sn_launch<19, true>(g, st, d_packed, V, S, viewdir_agg, rpt, d_vox, d_img, n_rays, nullptr, nullptr, nullptr, d_g_rgb_map, d_g_vox, d_g_img, parts);
-    else sn_launch<35, true>(g, st, d_packed, V, S, viewdir_agg, rpt, d_vox, d_img, n_rays, nullptr, nullptr, nullptr, d_g_rgb_map, d_g_vox, d_g_img, parts);
+    sn_dispatch(C, [&](auto c) {
+        hipLaunchKernelGGL((k_stage_nerf<decltype(c)::value, true>), dim3((unsigned)g), dim3(SN_THREADS), 0, st, d_packed, V, S, viewdir_agg, rpt, d_vox, d_img,
+                           n_rays, (float*)nullptr, (float*)nullptr, (float*)nullptr, d_g_rgb_map, d_g_vox, d_g_img, parts);
+    });
     LAUNCH_CHECK("k_stage_nerf (backward)");
     const int floats = sn_floats(C);
     hipLaunchKernelGGL(k_stage_reduce, dim3((floats + 255) / 256), dim3(256), 0, st, (const float*)parts, g, floats, d_g_packed);
