@@ -22,8 +22,9 @@
 //   pyramid  int64 [B * V][level][y][x][GDB_CP]   (GDB_CP = 20: the C_f + 3 = 19 channels + one pad that is never touched;
 //                                                  a tap row is 160 B, x0 | x1 are adjacent: 320 B per wave-instruction segment)
 //   volume   int64 [B][z][y][x][C_v]              (a tap row is 64 B, x0 | x1 128 B; one wave-instruction = the 8 taps of a sample)
-// Compiled with -ffp-contract=off like gdb_ops.hip: the coordinates, levels and tap indices below are the forward's own bits.
-#include "gdb_internal.h"
+// Compiled with -ffp-contract=off like gdb_ops.hip: the coordinates, levels and tap indices are the forward's own bits because they are
+// the forward's own code, the gdb_encode_geom.h helpers k_encode_vox / k_encode_views call (vox_coords; subray_cam, centre_tex, tex_taps).
+#include "gdb_encode_geom.h"
 
 #define EB_HDR_BYTES 256   // [0] uint32: max over the upstream of (float bits & 0x7fffffff)
 #define EB_ITEMS 64        // (view, sample) items per workgroup of k_encbwd_tex
@@ -98,21 +99,19 @@ __global__ void k_encbwd_vol(DevFrame f, const float* __restrict__ uvd, const in
     if (i >= total_clamped(total, n_alloc)) return;
     const int r = (int)(t & 63), c = r & 7, dx = (r >> 3) & 1, dy = (r >> 4) & 1, dz = (r >> 5) & 1;
     const int bi = batch_of(f.B, per_batch, i);
-    // k_encode_vox's coordinates
-    float x = gs_coord(uvd[i * 3 + 0], f.W), y = gs_coord(uvd[i * 3 + 1], f.H), z = gs_coord(uvd[i * 3 + 2], f.D);
-    float xf = floorf(x), yf = floorf(y), zf = floorf(z);
-    float wx = x - xf, wy = y - yf, wz = z - zf;
-    int xx = (int)xf + dx, yy = (int)yf + dy, zz = (int)zf + dz;
+    VoxCoords t3;
+    vox_coords(f, uvd, i, t3);
+    int xx = t3.x0 + dx, yy = t3.y0 + dy, zz = t3.z0 + dz;
     if (xx > f.W - 1 || yy > f.H - 1 || zz > f.D - 1 || xx < 0 || yy < 0 || zz < 0) return;   // the forward's out-of-range tap: weight 0
-    double w = (double)(dx ? wx : 1.f - wx) * (double)(dy ? wy : 1.f - wy) * (double)(dz ? wz : 1.f - wz);
+    double w = (double)(dx ? t3.wx : 1.f - t3.wx) * (double)(dy ? t3.wy : 1.f - t3.wy) * (double)(dz ? t3.wz : 1.f - t3.wz);
     double scale = eb_pow2(F - eb_exp(gb));
     size_t vox = (((size_t)bi * f.D + zz) * f.H + yy) * f.W + xx;
     eb_add(acc + vox * GDB_CV + c, w * (double)g_vox[i * GDB_CV + c] * scale);
 }
 
 // ---- 2b. pyramid scatter ---------------------------------------------------------------------------------------------------------
-// A workgroup takes EB_ITEMS samples of one view.  Its first wave recomputes each sample's texture coordinate and level exactly as
-// k_encode_views does and leaves the 8 taps (2 levels x 2 y x 2 x: texel index inside the (batch, view) pyramid, weight) in LDS;
+// A workgroup takes EB_ITEMS samples of one view.  Its first wave recomputes each sample's texture coordinate and level with
+// k_encode_views' helpers (centre_tex, tex_taps) and leaves the 8 taps (2 levels x 2 y x 2 x: texel index inside the (batch, view) pyramid, weight) in LDS;
 // then all lanes walk the (sample, tap, channel) slots, channel fastest, x tap next: 40 consecutive lanes = one 320-byte segment.
 template <int BB>
 __global__ void __launch_bounds__(EB_THREADS)
@@ -137,42 +136,30 @@ k_encbwd_tex(DevFrame f, const float* __restrict__ rays_xyz, const float* __rest
             float cc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < BB; ++s) {
-                float p[3];
+                float p[3], cam[3];
+                subray_point<BB>(rays_xyz, i, s, p);
+                subray_cam(sc, p, cam);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) p[c] = rays_xyz[((size_t)i * 3 + c) * BB + s];
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-                    cc[r] += sc[S_E + 4 * r] * p[0] + sc[S_E + 4 * r + 1] * p[1] + sc[S_E + 4 * r + 2] * p[2] + sc[S_E + 4 * r + 3];
+                for (int c = 0; c < 3; ++c) cc[c] += cam[c];
             }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) cc[c] = cc[c] / (float)BB;
-            float level = mip_level(cc[0], cc[1], cc[2], ball_radii[i], sc[S_PIXR]);
-            float ci[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) ci[r] = sc[S_KS + 3 * r] * cc[0] + sc[S_KS + 3 * r + 1] * cc[1] + sc[S_KS + 3 * r + 2] * cc[2];
-            float zc = fmaxf(ci[2], 1e-6f);
-            float tu = ci[0] / zc / (float)f.W, tv = ci[1] / zc / (float)f.H;
-            int l0, l1; float frac;
-            mip_select(level, f.levels, l0, l1, frac);
+            subray_mean<BB>(cc);
+            CentreTex ct;
+            centre_tex(f, sc, cc, ball_radii[i], ct);
             s_bi[tid] = bi;
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const int l = k ? l1 : l0;
-                const double wl = k ? (double)frac : 1.0 - (double)frac;
-                const bool on = k == 0 || frac > 0.f;   // the forward skips level l1 when frac == 0
-                int W, H; unsigned off;
-                level_geom(f, l, W, H, off);
-                int x0, x1, y0, y1; float fx, fy;
-                tex_coord(tu, W, x0, x1, fx);
-                tex_coord(tv, H, y0, y1, fy);
-                const int base = (int)(off / GDB_CP);
+                const double wl = k ? (double)ct.frac : 1.0 - (double)ct.frac;
+                const bool on = k == 0 || ct.frac > 0.f;   // the forward skips level l1 when frac == 0
+                TexTaps t;
+                tex_taps(f, k ? ct.l1 : ct.l0, ct.tu, ct.tv, t);
+                const int base = (int)(t.off / GDB_CP);
 #pragma unroll
                 for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
                     for (int dx = 0; dx < 2; ++dx) {
                         const int tap = k * 4 + dy * 2 + dx;
-                        s_idx[tid * 8 + tap] = on ? base + (dy ? y1 : y0) * W + (dx ? x1 : x0) : -1;
-                        s_w[tid * 8 + tap] = wl * (double)(dx ? fx : 1.f - fx) * (double)(dy ? fy : 1.f - fy);
+                        s_idx[tid * 8 + tap] = on ? base + (dy ? t.y1 : t.y0) * t.W + (dx ? t.x1 : t.x0) : -1;
+                        s_w[tid * 8 + tap] = wl * (double)(dx ? t.fx : 1.f - t.fx) * (double)(dy ? t.fy : 1.f - t.fy);
                     }
             }
         } else {
@@ -245,9 +232,7 @@ __global__ void k_encbwd_fold_img(DevFrame f, const unsigned* __restrict__ hdr, 
 static int eb_check(const GdbConfig* cfg, const GdbFrame* f, int64_t n_alloc) {
     int rc = gdb_check_cfg(cfg); if (rc) return rc;
     rc = gdb_check_frame(cfg, f, false); if (rc) return rc;
-    if (n_alloc < 1 || n_alloc > (int64_t)f->B * f->H * f->W * cfg->max_num_samples)
-        return gdb_fail(GDB_E_SHAPE, "n_alloc %lld outside 1..B*H*W*S_max", (long long)n_alloc);
-    return GDB_OK;
+    return gdb_check_n_alloc(cfg, f, n_alloc);
 }
 
 extern "C" int gdb_encode_backward_layout(const GdbConfig* cfg, const GdbFrame* shape, int64_t n_alloc, size_t out[4]) {
@@ -295,11 +280,9 @@ extern "C" int gdb_encode_backward(const GdbConfig* cfg, const GdbFrame* f, cons
     }
     if (g_img_feat) {
         dim3 g((unsigned)((n_alloc + EB_ITEMS - 1) / EB_ITEMS), f->V);
-        switch (cfg->bundle_size) {
-            case 1: hipLaunchKernelGGL(k_encbwd_tex<1>, g, dim3(EB_THREADS), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, g_rfd, hdr, F, accP); break;
-            case 2: hipLaunchKernelGGL(k_encbwd_tex<4>, g, dim3(EB_THREADS), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, g_rfd, hdr, F, accP); break;
-            default: hipLaunchKernelGGL(k_encbwd_tex<16>, g, dim3(EB_THREADS), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, g_rfd, hdr, F, accP); break;
-        }
+        bb_dispatch(cfg->bundle_size, [&](auto bb) {
+            hipLaunchKernelGGL(k_encbwd_tex<decltype(bb)::value>, g, dim3(EB_THREADS), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, g_rfd, hdr, F, accP);
+        });
         LAUNCH_CHECK("k_encbwd_tex");
         const size_t ntex = (size_t)f->B * f->V * f->H * f->W;
         hipLaunchKernelGGL(k_encbwd_fold_img, dim3((unsigned)((ntex + 255) / 256)), dim3(256), 0, st, d, hdr, F, accP, g_img_feat);

@@ -18,6 +18,9 @@ int gdb_check_frame(const GdbConfig* c, const GdbFrame* f, bool need_ptrs);
 
 // Segment bounds [start, end) of every bundle in the bundle-major sample list (k_seg_bounds, gdb_mlp.hip): zeroes seg, then launches.
 int gdb_seg_bounds_launch(const int64_t* idx, const int64_t* total, int64_t n_alloc, int64_t n_bundles, int32_t* seg, hipStream_t st);
+// Exclusive scan of n int32 counts (k_scan_block / k_scan_sums, gdb_ops.hip): offs[t] = offset inside t's block of SCAN_BLOCK entries, bsum[0 ..
+// nblk) = the blocks' own offsets, nblk = ceil(n / SCAN_BLOCK).  with_total also writes the grand total to bsum[nblk]: false when bsum holds nblk ints.
+int gdb_scan_launch(size_t n, int nblk, const int32_t* in, int32_t* offs, int32_t* bsum, bool with_total, hipStream_t st);
 
 // ---- fixed network sizes (every config of the reference: dtu_pretrain.yaml:17-42) ----------
 #define GDB_CF 16            // fpn.feat_dims[feat_level]
@@ -301,17 +304,6 @@ __device__ __forceinline__ float ball_unit_fast(float disk, float cosv) {
     return disk * cosv * __builtin_amdgcn_rsqf(t * t + 1.f);
 }
 
-// Footprint -> mip level.  bundle_sampler.py:343-348
-__device__ __forceinline__ float mip_level(float cx, float cy, float cz, float ball, float src_pixr) {
-    float dist = sqrtf(cx * cx + cy * cy + cz * cz);
-    float q = dist / cz;
-    float sec2 = q * q;
-    float r = dist / ball;
-    float a = sqrtf(fmaxf(r * r - 1.f, 1e-12f));
-    float c = sqrtf(fmaxf(sec2 - 1.f, 1e-12f));
-    return log2f((sec2 / (a + c)) / src_pixr);
-}
-
 // nvdiffrast level selection with mip_level_bias only: clamp to [0, L]; NaN -> 0.
 __device__ __forceinline__ void mip_select(float level, int L, int& l0, int& l1, float& frac) {
     float lv = fminf(fmaxf(level, 0.f), (float)L);  // fmaxf(NaN, 0) = 0
@@ -480,6 +472,7 @@ __device__ __forceinline__ void bundle_sample(const DevFrame& f, const Bundle<BB
 
 
 // Bilinear RGB at a projected point: 4-D grid_sample, border, align_corners=False.  :336
+// (k_posbwd_colour differentiates through these taps: img_taps, gdb_encode_geom.h, states them a second time - change both together)
 __device__ __forceinline__ void rgb_fetch(const float* __restrict__ img, int Ho, int Wo, float gx, float gy, float rgb[3]) {
     float x = gs_coord(gx, Wo), y = gs_coord(gy, Ho);
     float xf = floorf(x), yf = floorf(y);

@@ -6,7 +6,7 @@
 //
 // Compiled with -ffp-contract=off: the reference evaluates every torch op separately, so
 // a*b+c is two roundings unless written as fmaf() here on purpose.
-#include "gdb_internal.h"
+#include "gdb_encode_geom.h"
 #include <cstdio>
 #include <cstring>
 #include <cmath>
@@ -851,12 +851,21 @@ __global__ void k_scan_block(size_t n, const int32_t* __restrict__ in, int32_t* 
     if (threadIdx.x == 255) bsum[blockIdx.x] = wo + inc;
 }
 
-__global__ void k_scan_sums(int nblk, int32_t* __restrict__ bsum) {  // one thread; nblk <= a few thousand
+// one thread; nblk <= a few thousand.  with_total: also write the grand total to bsum[nblk] (the caller's buffer has that slot)
+__global__ void k_scan_sums(int nblk, int32_t* __restrict__ bsum, int with_total) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         int32_t acc = 0;
         for (int i = 0; i < nblk; ++i) { int32_t t = bsum[i]; bsum[i] = acc; acc += t; }
-        bsum[nblk] = acc;
+        if (with_total) bsum[nblk] = acc;
     }
+}
+
+int gdb_scan_launch(size_t n, int nblk, const int32_t* in, int32_t* offs, int32_t* bsum, bool with_total, hipStream_t st) {
+    hipLaunchKernelGGL(k_scan_block, dim3(nblk), dim3(256), 0, st, n, in, offs, bsum);
+    LAUNCH_CHECK("k_scan_block");
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(64), 0, st, nblk, bsum, with_total ? 1 : 0);
+    LAUNCH_CHECK("k_scan_sums");
+    return GDB_OK;
 }
 
 __global__ void k_scan_add(size_t n, const int32_t* __restrict__ bsum, int32_t* __restrict__ out) {
@@ -913,10 +922,7 @@ static int sample_impl(const DevFrame& d, const WsLayout& L, void* ws, float* ra
     unsigned g = (unsigned)((nb + 255) / 256);
     hipLaunchKernelGGL(k_counts<BB>, dim3(g), dim3(256), 0, st, d, cnt);
     LAUNCH_CHECK("k_counts");
-    hipLaunchKernelGGL(k_scan_block, dim3(L.nBlocksScan), dim3(256), 0, st, nb, cnt, offs, bsum);
-    LAUNCH_CHECK("k_scan_block");
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(64), 0, st, L.nBlocksScan, bsum);
-    LAUNCH_CHECK("k_scan_sums");
+    int rc = gdb_scan_launch(nb, L.nBlocksScan, cnt, offs, bsum, true, st); if (rc) return rc;
     hipLaunchKernelGGL(k_scan_add, dim3(g), dim3(256), 0, st, nb, bsum, offs);
     LAUNCH_CHECK("k_scan_add");
     hipLaunchKernelGGL(k_sample<BB>, dim3(g), dim3(256), 0, st, d, offs, bsum, L.nBlocksScan, rays_xyz, uvd, z_vals, ball,
@@ -937,11 +943,9 @@ extern "C" int gdb_sample(const GdbConfig* cfg, const GdbFrame* f, void* ws, flo
     WsLayout L = ws_layout(*cfg, *f);
     DevFrame d = dev_frame(*cfg, *f, L, ws);
     hipStream_t st = (hipStream_t)stream_;
-    switch (cfg->bundle_size) {
-        case 1: return sample_impl<1>(d, L, ws, rays_xyz, uvd, z_vals, ball, indices, per_batch, spb, total, st);
-        case 2: return sample_impl<4>(d, L, ws, rays_xyz, uvd, z_vals, ball, indices, per_batch, spb, total, st);
-        default: return sample_impl<16>(d, L, ws, rays_xyz, uvd, z_vals, ball, indices, per_batch, spb, total, st);
-    }
+    return bb_dispatch(cfg->bundle_size, [&](auto bb) {
+        return sample_impl<decltype(bb)::value>(d, L, ws, rays_xyz, uvd, z_vals, ball, indices, per_batch, spb, total, st);
+    });
 }
 
 // ============================================================================================
@@ -957,10 +961,8 @@ __global__ void k_encode_vox(DevFrame f, const float* __restrict__ uvd, const in
     int64_t i = t / GDB_CV; int c = (int)(t % GDB_CV);
     if (i >= n) return;
     int bi = batch_of(f.B, per_batch, i);
-    float x = gs_coord(uvd[i * 3 + 0], f.W), y = gs_coord(uvd[i * 3 + 1], f.H), z = gs_coord(uvd[i * 3 + 2], f.D);
-    float xf = floorf(x), yf = floorf(y), zf = floorf(z);
-    float wx = x - xf, wy = y - yf, wz = z - zf;
-    int x0 = (int)xf, y0 = (int)yf, z0 = (int)zf;
+    VoxCoords t3;
+    vox_coords(f, uvd, i, t3);
     const float* vol = f.feat_volume + ((size_t)bi * GDB_CV + c) * f.D * f.H * f.W;
     float acc = 0.f;
 #pragma unroll
@@ -969,9 +971,9 @@ __global__ void k_encode_vox(DevFrame f, const float* __restrict__ uvd, const in
         for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
             for (int dx = 0; dx < 2; ++dx) {
-                int xx = x0 + dx, yy = y0 + dy, zz = z0 + dz;
+                int xx = t3.x0 + dx, yy = t3.y0 + dy, zz = t3.z0 + dz;
                 bool in = xx <= f.W - 1 && yy <= f.H - 1 && zz <= f.D - 1;
-                float wgt = (dx ? wx : 1.f - wx) * (dy ? wy : 1.f - wy) * (dz ? wz : 1.f - wz);
+                float wgt = (dx ? t3.wx : 1.f - t3.wx) * (dy ? t3.wy : 1.f - t3.wy) * (dz ? t3.wz : 1.f - t3.wz);
                 float val = vol[((size_t)min(zz, f.D - 1) * f.H + min(yy, f.H - 1)) * f.W + min(xx, f.W - 1)];
                 acc += in ? val * wgt : 0.f;
             }
@@ -983,30 +985,25 @@ __global__ void k_encode_vox(DevFrame f, const float* __restrict__ uvd, const in
 // max_mip_level=L) as called at bundle_sampler.py:355-359.  Writes GDB_CFR floats.
 __device__ __forceinline__ void tex_level(const DevFrame& f, const float* __restrict__ pyr, int l, float u, float v,
                                           float4 out[GDB_CP / 4]) {
-    int W = f.lvlW[l], H = f.lvlH[l];
-    int x0, x1, y0, y1; float fx, fy;
-    tex_coord(u, W, x0, x1, fx);
-    tex_coord(v, H, y0, y1, fy);
-    const float4* base = (const float4*)(pyr + f.lvlOff[l]);  // chunk-planar: [chunk][y][x]
+    TexTaps t;
+    tex_taps(f, l, u, v, t);
+    const float4* base = (const float4*)(pyr + t.off);  // chunk-planar: [chunk][y][x]
 #pragma unroll
     for (int c = 0; c < GDB_CP / 4; ++c) {
-        const float4* pl = base + (size_t)c * H * W;
-        float4 top = lerp4(pl[(size_t)y0 * W + x0], pl[(size_t)y0 * W + x1], fx);
-        float4 bot = lerp4(pl[(size_t)y1 * W + x0], pl[(size_t)y1 * W + x1], fx);
-        out[c] = lerp4(top, bot, fy);
+        const float4* pl = base + (size_t)c * t.H * t.W;
+        float4 top = lerp4(pl[(size_t)t.y0 * t.W + t.x0], pl[(size_t)t.y0 * t.W + t.x1], t.fx);
+        float4 bot = lerp4(pl[(size_t)t.y1 * t.W + t.x0], pl[(size_t)t.y1 * t.W + t.x1], t.fx);
+        out[c] = lerp4(top, bot, t.fy);
     }
 }
 
-__device__ __forceinline__ void tex_fetch(const DevFrame& f, const float* __restrict__ pyr, float u, float v, float level,
-                                          float4 out[GDB_CP / 4]) {
-    int l0, l1; float frac;
-    mip_select(level, f.levels, l0, l1, frac);
-    tex_level(f, pyr, l0, u, v, out);
-    if (frac > 0.f) {
+__device__ __forceinline__ void tex_fetch(const DevFrame& f, const float* __restrict__ pyr, const CentreTex& t, float4 out[GDB_CP / 4]) {
+    tex_level(f, pyr, t.l0, t.tu, t.tv, out);
+    if (t.frac > 0.f) {
         float4 o1[GDB_CP / 4];
-        tex_level(f, pyr, l1, u, v, o1);
+        tex_level(f, pyr, t.l1, t.tu, t.tv, o1);
 #pragma unroll
-        for (int c = 0; c < GDB_CP / 4; ++c) out[c] = lerp4(out[c], o1[c], frac);
+        for (int c = 0; c < GDB_CP / 4; ++c) out[c] = lerp4(out[c], o1[c], t.frac);
     }
 }
 
@@ -1029,49 +1026,29 @@ __global__ void k_encode_views(DevFrame f, const float* __restrict__ rays_xyz, c
     float cw[3] = {0.f, 0.f, 0.f}, cc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < BB; ++s) {
-        float p[3];
+        float p[3], cam[3], im[3], zc, gx, gy, rgb[3];
+        subray_point<BB>(rays_xyz, i, s, p);
+        subray_cam(sc, p, cam);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { p[c] = rays_xyz[((size_t)i * 3 + c) * BB + s]; cw[c] += p[c]; }
-        float cam[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            cam[r] = sc[S_E + 4 * r] * p[0] + sc[S_E + 4 * r + 1] * p[1] + sc[S_E + 4 * r + 2] * p[2] + sc[S_E + 4 * r + 3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) cc[c] += cam[c];
-        float im[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) im[r] = sc[S_K + 3 * r] * cam[0] + sc[S_K + 3 * r + 1] * cam[1] + sc[S_K + 3 * r + 2] * cam[2];
-        float zc = fmaxf(im[2], 1e-6f);
-        float gx = 2.f * (im[0] / zc) / (float)f.Wo - 1.f, gy = 2.f * (im[1] / zc) / (float)f.Ho - 1.f;
-        float rgb[3];
+        for (int c = 0; c < 3; ++c) { cw[c] += p[c]; cc[c] += cam[c]; }
+        cam_to_grid(sc, cam, f.Wo, f.Ho, im, zc, gx, gy);
         rgb_fetch(img, f.Ho, f.Wo, gx, gy, rgb);
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[c * BB + s] = rgb[c];  // channel order c*b²+sub  :337
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { cw[c] = cw[c] / (float)BB; cc[c] = cc[c] / (float)BB; }
+    subray_mean<BB>(cw);
+    subray_mean<BB>(cc);
 
-    float level = mip_level(cc[0], cc[1], cc[2], ball_radii[i], sc[S_PIXR]);
-    float ci[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) ci[r] = sc[S_KS + 3 * r] * cc[0] + sc[S_KS + 3 * r + 1] * cc[1] + sc[S_KS + 3 * r + 2] * cc[2];
-    float zc = fmaxf(ci[2], 1e-6f);
-    float tu = ci[0] / zc / (float)f.W, tv = ci[1] / zc / (float)f.H;
+    CentreTex ct;
+    centre_tex(f, sc, cc, ball_radii[i], ct);
     float4 ft[GDB_CP / 4];
-    tex_fetch(f, f.pyr + ((size_t)bi * f.V + v) * f.pyrStride, tu, tv, level, ft);
+    tex_fetch(f, f.pyr + ((size_t)bi * f.V + v) * f.pyrStride, ct, ft);
     const float* ff = (const float*)ft;
 #pragma unroll
     for (int c = 0; c < GDB_CFR; ++c) o[3 * BB + c] = ff[c];
 
-    float td[3], sd[3], a[3], dif[3], dn[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a[c] = cw[c] - tc[T_O + c];
-    normalize3(a, td);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a[c] = cw[c] - sc[S_C + c];
-    normalize3(a, sd);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dif[c] = td[c] - sd[c];
+    float at[3], as[3], td[3], sd[3], dif[3], dn[3];
+    dir_code_fwd(cw, tc, sc, at, as, td, sd, dif);
     normalize3(dif, dn);
     o[3 * BB + GDB_CFR + 0] = dn[0]; o[3 * BB + GDB_CFR + 1] = dn[1]; o[3 * BB + GDB_CFR + 2] = dn[2];
     o[3 * BB + GDB_CFR + 3] = td[0] * sd[0] + td[1] * sd[1] + td[2] * sd[2];
@@ -1083,19 +1060,16 @@ extern "C" int gdb_encode(const GdbConfig* cfg, const GdbFrame* f, const void* w
     int rc = gdb_check_cfg(cfg); if (rc) return rc;
     rc = gdb_check_frame(cfg, f, true); if (rc) return rc;
     if (!ws || !rays_xyz || !uvd || !ball || !per_batch || !total || !out || !vox) return gdb_fail(GDB_E_BADARG, "NULL pointer");
-    if (n_alloc < 1 || n_alloc > (int64_t)f->B * f->H * f->W * cfg->max_num_samples)
-        return gdb_fail(GDB_E_SHAPE, "n_alloc %lld outside 1..B*H*W*S_max", (long long)n_alloc);
+    rc = gdb_check_n_alloc(cfg, f, n_alloc); if (rc) return rc;
     WsLayout L = ws_layout(*cfg, *f);
     DevFrame d = dev_frame(*cfg, *f, L, ws);
     hipStream_t st = (hipStream_t)stream_;
     hipLaunchKernelGGL(k_encode_vox, dim3((unsigned)((n_alloc * GDB_CV + 255) / 256)), dim3(256), 0, st, d, uvd, per_batch, total, vox);
     LAUNCH_CHECK("k_encode_vox");
     dim3 g((unsigned)((n_alloc + 127) / 128), f->V);
-    switch (cfg->bundle_size) {
-        case 1: hipLaunchKernelGGL(k_encode_views<1>, g, dim3(128), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, out); break;
-        case 2: hipLaunchKernelGGL(k_encode_views<4>, g, dim3(128), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, out); break;
-        default: hipLaunchKernelGGL(k_encode_views<16>, g, dim3(128), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, out); break;
-    }
+    bb_dispatch(cfg->bundle_size, [&](auto bb) {
+        hipLaunchKernelGGL(k_encode_views<decltype(bb)::value>, g, dim3(128), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, out);
+    });
     LAUNCH_CHECK("k_encode_views");
     return GDB_OK;
 }

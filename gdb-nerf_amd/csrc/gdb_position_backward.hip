@@ -3,8 +3,9 @@
 // gdb_encode_backward (the gathered values, 4.15) this is every path the colour loss takes through the hot path to a trainable tensor.
 //
 // Conventions (what torch autograd of the restatement does):
-//   * tap indices, fractions, the mip level and every clamp decision are the forward's own bits: the same gdb_internal.h helpers
-//     are called in the same order under the same compile contract (-ffp-contract=off); the derivative arithmetic is in double.
+//   * tap indices, fractions, the mip level and every clamp decision are the forward's own bits: no forward formula is restated here,
+//     they come from the gdb_encode_geom.h helpers that k_encode_vox / k_encode_views call (vox_coords; subray_cam, cam_to_grid;
+//     centre_tex with mip_level_parts, tex_taps; dir_code_fwd; img_taps states rgb_fetch's taps) under -ffp-contract=off; derivatives in double.
 //   * d/dx of a bilinear fetch = (1 - f_y)(t01 - t00) + f_y (t11 - t10), times the coordinate scale (W_o / 2 for the sub-ray colours,
 //     W_l per mip level, D / 2 for the volume's depth axis); a coordinate clamped by border / clamp-to-edge has derivative 0, equality
 //     included (torch's grid_sample rule).
@@ -22,8 +23,8 @@
 //   k_posbwd_colour  lane = (sample, sub-ray), views in order: sub-ray point -> camera -> image -> the 4 colour taps; adds to the
 //                    centre's share
 //   k_smpbwd         lane = bundle: its <= S_max samples in sample order -> the four range scalars (a segmented sum with a fixed
-//                    order; the sample offsets come from an exclusive scan of the counts, as in gdb_sample)
-#include "gdb_internal.h"
+//                    order; the sample offsets come from gdb_sample's own exclusive scan of the counts, gdb_scan_launch)
+#include "gdb_encode_geom.h"
 
 #define PB_THREADS 128
 
@@ -56,22 +57,18 @@ k_posbwd_vol(DevFrame f, const float* __restrict__ uvd, const int64_t* __restric
     float gd = 0.f;
     if (i < total_clamped(total, n_alloc)) {
         const int bi = batch_of(f.B, per_batch, i);
-        // k_encode_vox's coordinates
-        const float dn = uvd[i * 3 + 2];
-        float x = gs_coord(uvd[i * 3 + 0], f.W), y = gs_coord(uvd[i * 3 + 1], f.H), z = gs_coord(dn, f.D);
-        float xf = floorf(x), yf = floorf(y), zf = floorf(z);
-        float wx = x - xf, wy = y - yf;
-        int x0 = (int)xf, y0 = (int)yf, z0 = (int)zf;
+        VoxCoords t3;
+        vox_coords(f, uvd, i, t3);
+        const int z0 = t3.z0, z1 = min(z0 + 1, f.D - 1);
         const bool inz = z0 + 1 <= f.D - 1;
-        const int z1 = min(z0 + 1, f.D - 1);
         double w[4]; size_t o0[4], o1[4];
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
             for (int dx = 0; dx < 2; ++dx) {
-                const int xx = x0 + dx, yy = y0 + dy, t = dy * 2 + dx;
+                const int xx = t3.x0 + dx, yy = t3.y0 + dy, t = dy * 2 + dx;
                 const bool in = xx <= f.W - 1 && yy <= f.H - 1;   // the forward's out-of-range tap: weight 0
-                w[t] = in ? (double)(dx ? wx : 1.f - wx) * (double)(dy ? wy : 1.f - wy) : 0.0;
+                w[t] = in ? (double)(dx ? t3.wx : 1.f - t3.wx) * (double)(dy ? t3.wy : 1.f - t3.wy) : 0.0;
                 const size_t yx = (size_t)min(yy, f.H - 1) * f.W + min(xx, f.W - 1);
                 o0[t] = (size_t)z0 * f.H * f.W + yx; o1[t] = (size_t)z1 * f.H * f.W + yx;
             }
@@ -84,7 +81,7 @@ k_posbwd_vol(DevFrame f, const float* __restrict__ uvd, const int64_t* __restric
             for (int t = 0; t < 4; ++t) a += w[t] * ((inz ? (double)vol[o1[t]] : 0.0) - (double)vol[o0[t]]);
             s += (double)g_vox[i * GDB_CV + c] * a;
         }
-        gd = gs_inside(dn, f.D) ? (float)(s * (0.5 * (double)f.D)) : 0.f;
+        gd = gs_inside(uvd[i * 3 + 2], f.D) ? (float)(s * (0.5 * (double)f.D)) : 0.f;
     }
     g_uvd[i * 3 + 0] = 0.f; g_uvd[i * 3 + 1] = 0.f; g_uvd[i * 3 + 2] = gd;
 }
@@ -94,12 +91,10 @@ k_posbwd_vol(DevFrame f, const float* __restrict__ uvd, const int64_t* __restric
 // The four taps are contracted with the upstream first (S_t = sum_c g_c t_c, in double), then combined with the forward's fractions.
 __device__ __forceinline__ void pb_tex_level(const DevFrame& f, const float* __restrict__ pyr, int l, float u, float v,
                                              const float g[GDB_CP], double& val, double& du, double& dv) {
-    int W, H; unsigned off;
-    level_geom(f, l, W, H, off);
-    int x0, x1, y0, y1; float fx, fy;
-    tex_coord(u, W, x0, x1, fx);
-    tex_coord(v, H, y0, y1, fy);
-    const float4* base = (const float4*)(pyr + off);   // chunk-planar: [chunk][y][x]
+    TexTaps t;
+    tex_taps(f, l, u, v, t);
+    const int W = t.W, H = t.H, x0 = t.x0, x1 = t.x1, y0 = t.y0, y1 = t.y1; const float fx = t.fx, fy = t.fy;
+    const float4* base = (const float4*)(pyr + t.off);   // chunk-planar: [chunk][y][x]
     double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;
 #pragma unroll
     for (int c = 0; c < GDB_CP / 4; ++c) {
@@ -137,27 +132,20 @@ k_posbwd_centre(DevFrame f, const float* __restrict__ rays_xyz, const float* __r
         const float ball = ball_radii[i];
         for (int v = 0; v < f.V; ++v) {
             const float* sc = src_cam(f, bi, v);
-            // k_encode_views' centre
             float cw[3] = {0.f, 0.f, 0.f}, cc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < BB; ++s) {
-                float p[3];
+                float p[3], cam[3];
+                subray_point<BB>(rays_xyz, i, s, p);
+                subray_cam(sc, p, cam);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { p[c] = rays_xyz[((size_t)i * 3 + c) * BB + s]; cw[c] += p[c]; }
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-                    cc[r] += sc[S_E + 4 * r] * p[0] + sc[S_E + 4 * r + 1] * p[1] + sc[S_E + 4 * r + 2] * p[2] + sc[S_E + 4 * r + 3];
+                for (int c = 0; c < 3; ++c) { cw[c] += p[c]; cc[c] += cam[c]; }
             }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { cw[c] = cw[c] / (float)BB; cc[c] = cc[c] / (float)BB; }
-            const float level = mip_level(cc[0], cc[1], cc[2], ball, sc[S_PIXR]);
-            float ci[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) ci[r] = sc[S_KS + 3 * r] * cc[0] + sc[S_KS + 3 * r + 1] * cc[1] + sc[S_KS + 3 * r + 2] * cc[2];
-            const float zc = fmaxf(ci[2], 1e-6f);
-            const float tu = ci[0] / zc / (float)f.W, tv = ci[1] / zc / (float)f.H;
-            int l0, l1; float frac;
-            mip_select(level, f.levels, l0, l1, frac);
+            subray_mean<BB>(cw);
+            subray_mean<BB>(cc);
+            CentreTex ct;
+            centre_tex(f, sc, cc, ball, ct);
+            const float *ci = ct.ci, zc = ct.zc, frac = ct.frac;
 
             const float* gr = g_rfd + ((size_t)v * n_alloc + i) * P + 3 * BB;
             float g[GDB_CP];
@@ -166,9 +154,9 @@ k_posbwd_centre(DevFrame f, const float* __restrict__ rays_xyz, const float* __r
             g[GDB_CFR] = 0.f;
             const float* pyr = f.pyr + ((size_t)bi * f.V + v) * f.pyrStride;
             double val0, du0, dv0, val1 = 0.0, du1 = 0.0, dv1 = 0.0;
-            pb_tex_level(f, pyr, l0, tu, tv, g, val0, du0, dv0);
+            pb_tex_level(f, pyr, ct.l0, ct.tu, ct.tv, g, val0, du0, dv0);
             const bool blend = frac > 0.f;   // the forward skips level l1 when frac == 0; frac > 0 is also "level strictly inside (0, L)"
-            if (blend) pb_tex_level(f, pyr, l1, tu, tv, g, val1, du1, dv1);
+            if (blend) pb_tex_level(f, pyr, ct.l1, ct.tu, ct.tv, g, val1, du1, dv1);
             const double dfr = frac;
             const double g_tu = (1.0 - dfr) * du0 + dfr * du1, g_tv = (1.0 - dfr) * dv0 + dfr * dv1;
             const double g_level = blend ? val1 - val0 : 0.0;
@@ -183,14 +171,9 @@ k_posbwd_centre(DevFrame f, const float* __restrict__ rays_xyz, const float* __r
 #pragma unroll
                 for (int c = 0; c < 3; ++c) gcc[c] = (double)sc[S_KS + c] * gci0 + (double)sc[S_KS + 3 + c] * gci1 + (double)sc[S_KS + 6 + c] * gci2;
             }
-            // level <- mip_level(cc, ball, pixr), the forward's intermediates recomputed with its operations
+            // level <- mip_level(cc, ball, pixr), through the forward's own intermediates (mip_level_parts)
             {
-                const float dist = sqrtf(cc[0] * cc[0] + cc[1] * cc[1] + cc[2] * cc[2]);
-                const float q = dist / cc[2];
-                const float sec2 = q * q;
-                const float r = dist / ball;
-                const float A = r * r - 1.f, Cc = sec2 - 1.f;
-                const float a = sqrtf(fmaxf(A, 1e-12f)), c = sqrtf(fmaxf(Cc, 1e-12f));
+                const float dist = ct.mip.dist, q = ct.mip.q, sec2 = ct.mip.sec2, r = ct.mip.r, A = ct.mip.A, Cc = ct.mip.C, a = ct.mip.a, c = ct.mip.c;
                 const double apc = (double)(a + c);
                 const double m = (double)(sec2 / (a + c));
                 const double g_m = g_level / (m * 0.69314718055994530942);
@@ -216,12 +199,7 @@ k_posbwd_centre(DevFrame f, const float* __restrict__ rays_xyz, const float* __r
             // direction code: dn = normalize(td - sd), dot = td . sd, td = normalize(cw - o), sd = normalize(cw - C_v)
             {
                 float at[3], as[3], td[3], sd[3], dif[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { at[c] = cw[c] - tc[T_O + c]; as[c] = cw[c] - sc[S_C + c]; }
-                normalize3(at, td);
-                normalize3(as, sd);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) dif[c] = td[c] - sd[c];
+                dir_code_fwd(cw, tc, sc, at, as, td, sd, dif);
                 const double gdn[3] = {(double)gr[GDB_CFR], (double)gr[GDB_CFR + 1], (double)gr[GDB_CFR + 2]};
                 const double gdot = gr[GDB_CFR + 3];
                 double gdif[3], gtd[3], gsd[3], ga[3], gs[3];
@@ -258,43 +236,32 @@ k_posbwd_colour(DevFrame f, const float* __restrict__ rays_xyz, const int64_t* _
     if (i >= total_clamped(total, n_alloc)) return;   // (the tail rows were zeroed by k_posbwd_centre)
     const int bi = batch_of(f.B, per_batch, i);
     float p[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) p[c] = rays_xyz[((size_t)i * 3 + c) * BB + s];
+    subray_point<BB>(rays_xyz, i, s, p);
     const size_t plane = (size_t)f.Ho * f.Wo;
     double gp[3] = {0.0, 0.0, 0.0};
     for (int v = 0; v < f.V; ++v) {
         const float* sc = src_cam(f, bi, v);
         const float* img = f.src_images + ((size_t)bi * f.V + v) * 3 * plane;
-        // k_encode_views' projection of one sub-ray point
-        float cam[3], im[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            cam[r] = sc[S_E + 4 * r] * p[0] + sc[S_E + 4 * r + 1] * p[1] + sc[S_E + 4 * r + 2] * p[2] + sc[S_E + 4 * r + 3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) im[r] = sc[S_K + 3 * r] * cam[0] + sc[S_K + 3 * r + 1] * cam[1] + sc[S_K + 3 * r + 2] * cam[2];
-        const float zc = fmaxf(im[2], 1e-6f);
-        const float gx = 2.f * (im[0] / zc) / (float)f.Wo - 1.f, gy = 2.f * (im[1] / zc) / (float)f.Ho - 1.f;
-        // rgb_fetch's taps
-        float x = gs_coord(gx, f.Wo), y = gs_coord(gy, f.Ho);
-        float xf = floorf(x), yf = floorf(y);
-        float wx = x - xf, wy = y - yf;
-        int x0 = (int)xf, y0 = (int)yf;
-        const bool inx = x0 + 1 <= f.Wo - 1, iny = y0 + 1 <= f.Ho - 1;
-        const int x1 = min(x0 + 1, f.Wo - 1), y1 = min(y0 + 1, f.Ho - 1);
+        // k_encode_views' projection of one sub-ray point and its colour taps
+        float cam[3], im[3], zc, gx, gy;
+        subray_cam(sc, p, cam);
+        cam_to_grid(sc, cam, f.Wo, f.Ho, im, zc, gx, gy);
+        ImgTaps it;
+        img_taps(gx, gy, f.Ho, f.Wo, it);
         const float* gr = g_rfd + ((size_t)v * n_alloc + i) * P + s;
         double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;   // sum_c g_c tap_c; an out-of-range tap is worth 0
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float* pc = img + c * plane;
             const double g = gr[c * BB];
-            s00 += g * (double)pc[(size_t)y0 * f.Wo + x0];
-            s01 += g * (double)pc[(size_t)y0 * f.Wo + x1];
-            s10 += g * (double)pc[(size_t)y1 * f.Wo + x0];
-            s11 += g * (double)pc[(size_t)y1 * f.Wo + x1];
+            s00 += g * (double)pc[(size_t)it.y0 * f.Wo + it.x0];
+            s01 += g * (double)pc[(size_t)it.y0 * f.Wo + it.x1];
+            s10 += g * (double)pc[(size_t)it.y1 * f.Wo + it.x0];
+            s11 += g * (double)pc[(size_t)it.y1 * f.Wo + it.x1];
         }
-        if (!inx) { s01 = 0.0; s11 = 0.0; }
-        if (!iny) { s10 = 0.0; s11 = 0.0; }
-        const double dwx = wx, dwy = wy;
+        if (!it.inx) { s01 = 0.0; s11 = 0.0; }
+        if (!it.iny) { s10 = 0.0; s11 = 0.0; }
+        const double dwx = it.wx, dwy = it.wy;
         // pixel coordinate <- grid coordinate: (W_o / 2) (2 / W_o) = 1
         const double g_px = gs_inside(gx, f.Wo) ? (1.0 - dwy) * (s01 - s00) + dwy * (s11 - s10) : 0.0;
         const double g_py = gs_inside(gy, f.Ho) ? (1.0 - dwx) * (s10 - s00) + dwx * (s11 - s01) : 0.0;
@@ -316,33 +283,6 @@ k_posbwd_colour(DevFrame f, const float* __restrict__ rays_xyz, const int64_t* _
 }
 
 // ---- sample -----------------------------------------------------------------------------------------------------------------------
-// Exclusive scan of the int32 counts, as gdb_sample runs it: per-block scan, serial scan of the block sums, add-back.
-__global__ void k_smpbwd_scan_block(size_t n, const int32_t* __restrict__ in, int32_t* __restrict__ out, int32_t* __restrict__ bsum) {
-    __shared__ int32_t wsum[4];
-    size_t base = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x * 4;
-    int32_t v[4], s = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[i] = base + i < n ? in[base + i] : 0; s += v[i]; }
-    int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int32_t inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { int32_t y = __shfl_up(inc, o); if (lane >= o) inc += y; }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int32_t wo = 0;
-    for (int i = 0; i < wid; ++i) wo += wsum[i];
-    int32_t ex = wo + inc - s;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { if (base + i < n) out[base + i] = ex; ex += v[i]; }
-    if (threadIdx.x == 255) bsum[blockIdx.x] = wo + inc;
-}
-__global__ void k_smpbwd_scan_sums(int nblk, int32_t* __restrict__ bsum) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        int32_t acc = 0;
-        for (int i = 0; i < nblk; ++i) { int32_t t = bsum[i]; bsum[i] = acc; acc += t; }
-    }
-}
-
 template <int BB>
 __global__ void __launch_bounds__(PB_THREADS)
 k_smpbwd(DevFrame f, const int32_t* __restrict__ spb, const int32_t* __restrict__ offs, const int32_t* __restrict__ bsum,
@@ -411,12 +351,6 @@ k_smpbwd(DevFrame f, const int32_t* __restrict__ spb, const int32_t* __restrict_
 }
 
 // ---- entries -----------------------------------------------------------------------------------------------------------------------
-static int pb_check_n(const GdbConfig* cfg, const GdbFrame* f, int64_t n_alloc) {
-    if (n_alloc < 1 || n_alloc > (int64_t)f->B * f->H * f->W * cfg->max_num_samples)
-        return gdb_fail(GDB_E_SHAPE, "n_alloc %lld outside 1..B*H*W*S_max", (long long)n_alloc);
-    return GDB_OK;
-}
-
 extern "C" int gdb_encode_position_backward(const GdbConfig* cfg, const GdbFrame* f, const void* ws, const float* rays_xyz,
                                             const float* uvd, const float* ball, const int64_t* per_batch, const int64_t* total,
                                             int64_t n_alloc, const float* g_rfd, const float* g_vox, float* g_rays_xyz, float* g_uvd,
@@ -425,7 +359,7 @@ extern "C" int gdb_encode_position_backward(const GdbConfig* cfg, const GdbFrame
     rc = gdb_check_frame(cfg, f, true); if (rc) return rc;
     if (!ws || !rays_xyz || !uvd || !ball || !per_batch || !total || !g_rfd || !g_vox) return gdb_fail(GDB_E_BADARG, "NULL pointer");
     if (!g_rays_xyz && !g_uvd && !g_ball) return gdb_fail(GDB_E_BADARG, "all three outputs are NULL");
-    rc = pb_check_n(cfg, f, n_alloc); if (rc) return rc;
+    rc = gdb_check_n_alloc(cfg, f, n_alloc); if (rc) return rc;
     WsLayout L = ws_layout(*cfg, *f);
     DevFrame d = dev_frame(*cfg, *f, L, ws);
     hipStream_t st = (hipStream_t)stream_;
@@ -435,21 +369,18 @@ extern "C" int gdb_encode_position_backward(const GdbConfig* cfg, const GdbFrame
         LAUNCH_CHECK("k_posbwd_vol");
     }
     if (g_rays_xyz || g_ball) {
-        switch (cfg->bundle_size) {
-            case 1: hipLaunchKernelGGL(k_posbwd_centre<1>, dim3(gn), dim3(PB_THREADS), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, g_rfd, g_rays_xyz, g_ball); break;
-            case 2: hipLaunchKernelGGL(k_posbwd_centre<4>, dim3(gn), dim3(PB_THREADS), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, g_rfd, g_rays_xyz, g_ball); break;
-            default: hipLaunchKernelGGL(k_posbwd_centre<16>, dim3(gn), dim3(PB_THREADS), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, g_rfd, g_rays_xyz, g_ball); break;
-        }
+        bb_dispatch(cfg->bundle_size, [&](auto bb) {
+            hipLaunchKernelGGL(k_posbwd_centre<decltype(bb)::value>, dim3(gn), dim3(PB_THREADS), 0, st, d, rays_xyz, ball, per_batch, total, n_alloc, g_rfd,
+                               g_rays_xyz, g_ball);
+        });
         LAUNCH_CHECK("k_posbwd_centre");
     }
     if (g_rays_xyz) {
         const int bb = cfg->bundle_size * cfg->bundle_size;
         const unsigned gc = (unsigned)((n_alloc * bb + PB_THREADS - 1) / PB_THREADS);
-        switch (cfg->bundle_size) {
-            case 1: hipLaunchKernelGGL(k_posbwd_colour<1>, dim3(gc), dim3(PB_THREADS), 0, st, d, rays_xyz, per_batch, total, n_alloc, g_rfd, g_rays_xyz); break;
-            case 2: hipLaunchKernelGGL(k_posbwd_colour<4>, dim3(gc), dim3(PB_THREADS), 0, st, d, rays_xyz, per_batch, total, n_alloc, g_rfd, g_rays_xyz); break;
-            default: hipLaunchKernelGGL(k_posbwd_colour<16>, dim3(gc), dim3(PB_THREADS), 0, st, d, rays_xyz, per_batch, total, n_alloc, g_rfd, g_rays_xyz); break;
-        }
+        bb_dispatch(cfg->bundle_size, [&](auto bb) {
+            hipLaunchKernelGGL(k_posbwd_colour<decltype(bb)::value>, dim3(gc), dim3(PB_THREADS), 0, st, d, rays_xyz, per_batch, total, n_alloc, g_rfd, g_rays_xyz);
+        });
         LAUNCH_CHECK("k_posbwd_colour");
     }
     return GDB_OK;
@@ -464,23 +395,20 @@ extern "C" int gdb_sample_backward(const GdbConfig* cfg, const GdbFrame* f, cons
     if (!ws || !spb || !total || !scratch) return gdb_fail(GDB_E_BADARG, "NULL pointer");
     if (!g_rays_xyz && !g_uvd && !g_z_vals && !g_ball) return gdb_fail(GDB_E_BADARG, "all four upstream gradients are NULL");
     if (!g_depth_range && !g_vol_range) return gdb_fail(GDB_E_BADARG, "both outputs are NULL");
-    rc = pb_check_n(cfg, f, n_alloc); if (rc) return rc;
+    rc = gdb_check_n_alloc(cfg, f, n_alloc); if (rc) return rc;
     WsLayout L = ws_layout(*cfg, *f);
     DevFrame d = dev_frame(*cfg, *f, L, ws);
     hipStream_t st = (hipStream_t)stream_;
     const size_t nb = (size_t)f->B * f->H * f->W;
     int32_t* offs = (int32_t*)scratch;   // [nb] offsets inside a scan block, then [nBlocksScan] block offsets
     int32_t* bsum = offs + nb;
-    hipLaunchKernelGGL(k_smpbwd_scan_block, dim3(L.nBlocksScan), dim3(256), 0, st, nb, spb, offs, bsum);
-    LAUNCH_CHECK("k_smpbwd_scan_block");
-    hipLaunchKernelGGL(k_smpbwd_scan_sums, dim3(1), dim3(64), 0, st, L.nBlocksScan, bsum);
-    LAUNCH_CHECK("k_smpbwd_scan_sums");
+    // gdb_sample's scan, without the grand total: the scratch has exactly nBlocksScan block slots
+    rc = gdb_scan_launch(nb, L.nBlocksScan, spb, offs, bsum, false, st); if (rc) return rc;
     const unsigned g = (unsigned)((nb + PB_THREADS - 1) / PB_THREADS);
-    switch (cfg->bundle_size) {
-        case 1: hipLaunchKernelGGL(k_smpbwd<1>, dim3(g), dim3(PB_THREADS), 0, st, d, spb, offs, bsum, total, n_alloc, g_rays_xyz, g_uvd, g_z_vals, g_ball, g_depth_range, g_vol_range); break;
-        case 2: hipLaunchKernelGGL(k_smpbwd<4>, dim3(g), dim3(PB_THREADS), 0, st, d, spb, offs, bsum, total, n_alloc, g_rays_xyz, g_uvd, g_z_vals, g_ball, g_depth_range, g_vol_range); break;
-        default: hipLaunchKernelGGL(k_smpbwd<16>, dim3(g), dim3(PB_THREADS), 0, st, d, spb, offs, bsum, total, n_alloc, g_rays_xyz, g_uvd, g_z_vals, g_ball, g_depth_range, g_vol_range); break;
-    }
+    bb_dispatch(cfg->bundle_size, [&](auto bb) {
+        hipLaunchKernelGGL(k_smpbwd<decltype(bb)::value>, dim3(g), dim3(PB_THREADS), 0, st, d, spb, offs, bsum, total, n_alloc, g_rays_xyz, g_uvd,
+                           g_z_vals, g_ball, g_depth_range, g_vol_range);
+    });
     LAUNCH_CHECK("k_smpbwd");
     return GDB_OK;
 }

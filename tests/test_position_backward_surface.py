@@ -91,6 +91,42 @@ def test_the_new_file_is_built_with_contraction_off_and_uses_no_private_memory(l
         assert u["scratch_bytes_per_lane"] == 0 and u["vgpr_spill"] == 0, (name, u)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("Ho, Wo, scan_blocks", [(16, 24, 1), (64, 80, 2)])
+def test_sample_backward_stays_inside_its_documented_scratch(lib, Ho, Wo, scan_blocks):
+    """`gdb_sample_backward`'s scratch is documented as 4 * (B*H*W + ceil(B*H*W / 1024)) bytes: the offsets inside a scan block, then one
+    offset per block - and no slot for the grand total `gdb_sample`'s own scan leaves behind its block offsets.  Called through ctypes
+    with 8 sentinel words behind that size, it leaves them alone and returns the bits of `engine.sample_backward`; with two scan
+    blocks the block offsets are read."""
+    import numpy as np
+    from conftest import FRAME_KEYS
+    from gdb_nerf_amd import synthetic
+    from gdb_nerf_amd.engine import HotPathEngine
+    fr = synthetic.make_frame(Ho, Wo, V=2, B=1, bundle_size=2, scene="dtu", seed=11)
+    eng = HotPathEngine(bundle_size=2)
+    eng.prepare({k: torch.tensor(np.ascontiguousarray(fr[k]), dtype=torch.float32, device="cuda") for k in FRAME_KEYS})
+    s = eng.sample()
+    nb, n = eng.n_bundles, int(s["total"].item())
+    assert nb == (Ho // 2) * (Wo // 2) and (nb + 1023) // 1024 == scan_blocks and n >= nb
+    gen = torch.Generator().manual_seed(5)
+    ups = [torch.randn(shape, generator=gen).cuda() for shape in ((n, 3, 4), (n, 3), (n,), (n,))]
+    spb, total = s["samples_per_bundle"], s["total"]
+    want = eng.sample_backward(spb, total, *ups)
+    documented, sentinel = nb + (nb + 1023) // 1024, 0x5A5A5A5A
+    scratch = torch.full((documented + 8,), sentinel, dtype=torch.int32, device="cuda")
+    f = eng._need_frame()
+    got = [torch.empty((f.B, 2, f.H, f.W), device="cuda") for _ in range(2)]
+    _lib.check(eng.lib.gdb_sample_backward(C.byref(eng.cfg), C.byref(f), eng._ws.data_ptr(), spb.data_ptr(), total.data_ptr(), n,
+                                           *(u.data_ptr() for u in ups), got[0].data_ptr(), got[1].data_ptr(), scratch.data_ptr(),
+                                           eng._stream()))
+    torch.cuda.synchronize()
+    assert scratch[documented:].tolist() == [sentinel] * 8
+    assert not (scratch[:documented] == sentinel).any()   # ... and the documented part was all written
+    for g, w, name in zip(got, want, ("g_depth_range", "g_vol_range")):
+        assert torch.equal(g.view(torch.int32), w.view(torch.int32)), name
+        assert g.abs().max() > 0, name
+
+
 class _Entered(Exception):
     pass
 
