@@ -25,7 +25,8 @@ def _t(x) -> torch.Tensor:
 
 def build_rays(tar_ext: torch.Tensor, tar_int: torch.Tensor, Ho: int, Wo: int) -> Dict[str, torch.Tensor]:
     """bundle_sampler.py:30-74: pixel-centre grid, unnormalised directions [x, y, 1] (R_c2w K^-1)^T, pixel radius."""
-    ys, xs = torch.meshgrid(torch.arange(Ho, dtype=torch.float32) + 0.5, torch.arange(Wo, dtype=torch.float32) + 0.5, indexing="ij")
+    dt = tar_int.dtype                                                                        # float32 as the reference; float64 for a referee
+    ys, xs = torch.meshgrid(torch.arange(Ho, dtype=dt) + 0.5, torch.arange(Wo, dtype=dt) + 0.5, indexing="ij")
     uv = torch.stack((2.0 * xs / Wo - 1.0, 2.0 * ys / Ho - 1.0), dim=-1)                      # :53-56
     c2w = torch.inverse(tar_ext)                                                              # :62
     pix = torch.stack((xs, ys, torch.ones_like(xs)), dim=-1).reshape(1, -1, 3)
@@ -37,11 +38,30 @@ def build_rays(tar_ext: torch.Tensor, tar_int: torch.Tensor, Ho: int, Wo: int) -
 
 def sample_bundles(rays, depth_range, vol_range, near, far, b, S_max, global_num_depth, inv_depth, adaptive):
     """bundle_sampler.py:76-265: bundle assembly, (adaptive) sample counts, bundle-major / sample-minor compaction, per-sample
-    geometry."""
+    geometry.  In the dtype of `depth_range`."""
+    B, Ho, Wo, _ = rays["rays_d"].shape
+    nb = B * (Ho // b) * (Wo // b)
+    dr = 1.0 / depth_range if inv_depth else depth_range                                      # :224-226
+    if inv_depth:
+        near, far = 1.0 / near, 1.0 / far
+    nearv, farv = dr[:, 0].reshape(nb), dr[:, 1].reshape(nb)
+    if adaptive:                                                                              # :156-191
+        miniv = ((far - near).abs() / global_num_depth)[:, None, None].expand(B, Ho // b, Wo // b).reshape(nb)   # :227-232
+        spb = torch.ceil((farv - nearv).abs() / miniv).clamp(1, S_max)                        # :179
+    else:
+        spb = torch.full((nb,), float(S_max), dtype=depth_range.dtype)
+    return sample_bundles_counted(rays, depth_range, vol_range, b, inv_depth, spb.to(torch.int64))
+
+
+def sample_bundles_counted(rays, depth_range, vol_range, b, inv_depth, cnt):
+    """`sample_bundles` with the per-bundle sample counts `cnt` (int64, (n_bundles,)) given as data: everything after the counts, the
+    same operations in the same order, in the dtype of `depth_range`.  `ceil` can differ between dtypes, so a float64 referee of a
+    float32 run takes that run's counts; `sample_bundles` itself ends in this function, so the two cannot drift apart."""
+    dt = depth_range.dtype
     B, Ho, Wo, _ = rays["rays_d"].shape
     H, W, bb = Ho // b, Wo // b, b * b
     if inv_depth:                                                                             # :224-226
-        depth_range, vol_range, near, far = 1.0 / depth_range, 1.0 / vol_range, 1.0 / near, 1.0 / far
+        depth_range, vol_range = 1.0 / depth_range, 1.0 / vol_range
     d = rays["rays_d"].reshape(B, H, b, W, b, 3).permute(0, 1, 3, 5, 2, 4).reshape(B, H, W, 3, bb)   # channel c, sub-ray by*b+bx (:100)
     bundle_d = d.mean(dim=-1)                                                                 # :99
     cos = (bundle_d * rays["z_axis"][:, None, None]).sum(-1) / bundle_d.norm(dim=-1)          # :102
@@ -49,15 +69,10 @@ def sample_bundles(rays, depth_range, vol_range, near, far, b, S_max, global_num
     disk = b * rays["tar_pixel_radius"]                                                       # :106
     nb = B * H * W
     nearv, farv = depth_range[:, 0].reshape(nb), depth_range[:, 1].reshape(nb)
-    if adaptive:                                                                              # :156-191
-        miniv = ((far - near).abs() / global_num_depth)[:, None, None].expand(B, H, W).reshape(nb)   # :227-232
-        spb = torch.ceil((farv - nearv).abs() / miniv).clamp(1, S_max)                        # :179
-    else:
-        spb = torch.full((nb,), float(S_max))
-    cnt = spb.to(torch.int64)
+    spb = cnt.to(dt)
     indices = torch.repeat_interleave(torch.arange(nb), cnt)                                  # :182-189
     first = torch.cumsum(cnt, 0) - cnt
-    k = (torch.arange(indices.numel()) - first[indices]).to(torch.float32)
+    k = (torch.arange(indices.numel()) - first[indices]).to(dt)
     n_i, f_i, c_i = nearv[indices], farv[indices], spb[indices]
     step = (f_i - n_i) / c_i
     t0, t1 = n_i + step * k, n_i + step * (k + 1.0)                                           # :183
@@ -179,6 +194,11 @@ def nerf_mlp(w: Dict[str, torch.Tensor], vox: torch.Tensor, x: torch.Tensor, fea
 def render_bundles(w, rfd, vox, z, indices, n_bundles, inv_depth, feat_dim=16, viewdir_agg=True):
     """network.py:54-91 with utils.py:19-43 (alpha, exclusive transmittance per bundle, normalisation) and utils.py:88-121."""
     sigma, feat = nerf_mlp(w, vox, rfd, feat_dim, viewdir_agg)
+    return accumulate(render_weights(sigma, indices, n_bundles), feat, z, indices, n_bundles, inv_depth)
+
+
+def render_weights(sigma, indices, n_bundles, den_floor=1e-6):
+    """utils.py:19-43: alpha, exclusive transmittance per bundle, weights normalised by max(their sum, den_floor)."""
     alpha = 1.0 - torch.exp(-sigma)                                                           # utils.py:34
     cnt = torch.bincount(indices, minlength=n_bundles)
     first = torch.cumsum(cnt, 0) - cnt
@@ -188,8 +208,12 @@ def render_bundles(w, rfd, vox, z, indices, n_bundles, inv_depth, feat_dim=16, v
     tab[indices, k + 1] = 1.0 - alpha                                                         # padded per-bundle table
     T = torch.cumprod(tab, dim=1)[indices, k]                                                 # exclusive product   (nerfacc, utils.py:35)
     wgt = alpha * T
-    den = torch.zeros(n_bundles).index_add_(0, indices, wgt).clamp(min=1e-6)                  # utils.py:38-41
-    wgt = wgt / den[indices]
+    den = torch.zeros(n_bundles).index_add_(0, indices, wgt).clamp(min=den_floor)             # utils.py:38-41
+    return wgt / den[indices]
+
+
+def accumulate(wgt, feat, z, indices, n_bundles, inv_depth):
+    """utils.py:88-121 with network.py:83-89: per bundle sum of w [feat | z | 1] -> (bundle_feat, depth, opacity)."""
     zz = 1.0 / z if inv_depth else z                                                          # network.py:83-84
     vals = torch.cat((feat, zz[:, None], torch.ones_like(zz)[:, None]), dim=1) * wgt[:, None]   # utils.py:109-110
     acc = torch.zeros(n_bundles, vals.shape[1]).index_add_(0, indices, vals)

@@ -15,8 +15,8 @@ im_x / z - 1/2, im_y / z - 1/2, every view's unclamped mip level, and every view
 blended levels (texture, image and level clamps all sit on integers).  m_i < 1e-4 is excluded; at most 5 % of a case's samples may
 be, asserted.  No clamp_min floor may be near either: projected depths > 1e-3, both radicands of the mip level > 1e-9, asserted.
 
-`sample` is refereed at its own boundary by a test-local restatement of `sample_bundles` that takes the counts as data (ceil can differ
-between dtypes; the counts are the HIP forward's); at float32 it is bit-equal to `oracle_t.sample_bundles`, asserted.  Random
+`sample` is refereed at its own boundary by `oracle_t.sample_bundles_counted`, the restatement of `sample_bundles` that takes the counts as
+data (ceil can differ between dtypes; the counts are the HIP forward's); at float32 it is bit-equal to `oracle_t.sample_bundles`, asserted.  Random
 upstreams on all four outputs, same rule, nothing excluded.  One end-to-end case chains both entries against autograd of the chained
 restatements.
 
@@ -129,44 +129,7 @@ def kink_margins(fr, smp, spb, b, levels):
     return m.numpy(), min_depth, min_rad
 
 
-def sample_restated(rays, depth_range, vol_range, b, inv_depth, cnt):
-    """`oracle_t.sample_bundles` (bundle_sampler.py:76-265) with the per-bundle counts `cnt` (int64) given as data: the same operations
-    in the same order, in the dtype of the ranges."""
-    dt = depth_range.dtype
-    B, Ho, Wo, _ = rays["rays_d"].shape
-    H, W, bb = Ho // b, Wo // b, b * b
-    if inv_depth:
-        depth_range, vol_range = 1.0 / depth_range, 1.0 / vol_range
-    d = rays["rays_d"].reshape(B, H, b, W, b, 3).permute(0, 1, 3, 5, 2, 4).reshape(B, H, W, 3, bb)
-    bundle_d = d.mean(dim=-1)
-    cos = (bundle_d * rays["z_axis"][:, None, None]).sum(-1) / bundle_d.norm(dim=-1)
-    uvm = rays["uv"].reshape(H, b, W, b, 2).mean(dim=(1, 3))
-    disk = b * rays["tar_pixel_radius"]
-    nb = B * H * W
-    nearv, farv = depth_range[:, 0].reshape(nb), depth_range[:, 1].reshape(nb)
-    spb = cnt.to(dt)
-    indices = torch.repeat_interleave(torch.arange(nb), cnt)
-    first = torch.cumsum(cnt, 0) - cnt
-    k = (torch.arange(indices.numel()) - first[indices]).to(dt)
-    n_i, f_i, c_i = nearv[indices], farv[indices], spb[indices]
-    step = (f_i - n_i) / c_i
-    t0, t1 = n_i + step * k, n_i + step * (k + 1.0)
-    z = 0.5 * (t0 + t1)
-    vn, vf = vol_range[:, 0].reshape(nb)[indices], vol_range[:, 1].reshape(nb)[indices]
-    dn = 2.0 * (z - vn) / (vf - vn) - 1.0
-    if inv_depth:
-        z = 1.0 / z
-    bidx = indices // (H * W)
-    uvd = torch.cat((uvm.reshape(1, H * W, 2).expand(B, -1, -1).reshape(nb, 2)[indices], dn[:, None]), dim=1)
-    o = rays["rays_o"][bidx]
-    xyz = o[:, :, None] + d.reshape(nb, 3, bb)[indices] * z[:, None, None]
-    ctr = xyz.mean(dim=-1)
-    dist = (ctr - o).norm(dim=-1)
-    cosb, diskb = cos.reshape(nb), disk[:, None, None].expand(B, H, W).reshape(nb)
-    tt = torch.sqrt(torch.clamp(1.0 / (cosb * cosb) - 1.0, min=1e-12)) - diskb
-    unit = diskb * cosb / torch.sqrt(tt * tt + 1.0)
-    per_batch = torch.zeros(B, dtype=torch.int64).index_add_(0, torch.arange(nb) // (H * W), cnt)
-    return {"rays_xyz": xyz, "uvd": uvd, "z_vals": z, "ball_radii": unit[indices] * dist, "indices": indices, "samples_per_batch": per_batch}
+sample_restated = oracle_t.sample_bundles_counted   # the one counts-as-data restatement (its float32 bit-equality is asserted below)
 
 
 def rays_of(fr, dtype):
