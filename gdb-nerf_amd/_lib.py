@@ -153,6 +153,11 @@ _SIGNATURES = {
     "gdb_cost_reg_train": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 4 + [C.POINTER(_P), C.c_float, C.c_float, _P, C.c_size_t, _P, _P, _P, _P]),
     "gdb_cost_reg_train_backward": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 4 + [C.POINTER(_P), _P, _P, _P, C.c_size_t, _P, C.c_size_t,
                                                 C.POINTER(_P), _P]),
+    "gdb_cost_reg_train_cost_grad_bytes": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_size_t)]),
+    "gdb_cost_reg_train_backward_cost": (C.c_int, [C.c_int32] * 4 + [_P] + [C.c_int32] * 4 + [C.POINTER(_P), _P, _P, _P, C.c_size_t, _P, C.c_size_t,
+                                                     C.POINTER(_P), _P, _P, C.c_size_t, _P]),
+    "gdb_feature_volume_backward_workspace_bytes": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "gdb_feature_volume_backward": (C.c_int, [_P] * 7 + [C.c_int32] * 9 + [_P, C.c_size_t, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

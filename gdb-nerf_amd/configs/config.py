@@ -24,7 +24,8 @@ DEFAULTS = {
              "sampler_meta": {"input_views_num": [], "input_views_prob": []}, "eval_depth": False, "eval_center": False,
              "hip_metrics": False, "lpips_weights": ""},
     # hip_cost_reg_train: the 3-D U-Nets in training mode, forward and backward, on the HIP library (costvol.CostRegTrain)
-    "mvs": {"hip_cost_reg_train": False},
+    # cost_volume_grad: on CUDA the plane sweep carries a graph to the feature maps and the hypotheses (costvol.FeatureVolumeFunction)
+    "mvs": {"hip_cost_reg_train": False, "cost_volume_grad": False},
 }
 
 

@@ -40,6 +40,64 @@ def build_feature_volume(src_feat, src_exts, src_ints, tar_exts, tar_ints, depth
     return out
 
 
+def feature_volume_backward(src_feat, src_exts, src_ints, tar_exts, tar_ints, depth_values, g_cost, inv_depth: bool,
+                            want_src_feat: bool = True, want_depth_values: bool = True, workspace: torch.Tensor = None):
+    """gdb_feature_volume_backward: (g_src_feat (B, V, C, Hs, Ws) or None, g_depth_values (B, D, Ht, Wt) or None) from
+    the forward's inputs and the upstream g_cost (B, C, D, Ht, Wt), on the current stream.  `workspace`: a contiguous CUDA tensor of
+    at least `feature_volume_backward_workspace_bytes` bytes (its contents do not matter); by default allocated per call."""
+    lib = _lib.load()
+    if not (want_src_feat or want_depth_values):
+        raise ValueError("feature_volume_backward: neither output is requested")
+    B, V, Cc, Hs, Ws = src_feat.shape
+    D, Ht, Wt = depth_values.shape[1:]
+    if depth_values.shape[0] != B or tuple(src_exts.shape) != (B, V, 4, 4) or tuple(src_ints.shape) != (B, V, 3, 3) \
+            or tuple(tar_exts.shape) != (B, 4, 4) or tuple(tar_ints.shape) != (B, 3, 3) or tuple(g_cost.shape) != (B, Cc, D, Ht, Wt):
+        raise ValueError("inconsistent cost-volume shapes")
+    args = [_c(t, n) for t, n in ((src_feat, "src_feat"), (src_exts, "src_exts"), (src_ints, "src_ints"), (tar_exts, "tar_exts"),
+                                  (tar_ints, "tar_ints"), (depth_values, "depth_values"), (g_cost, "g_cost"))]
+    nbytes = feature_volume_backward_workspace_bytes(B, V, Cc, Hs, Ws, D, Ht, Wt)[0]
+    dev = src_feat.device
+    if workspace is None:   # per call from torch's caching allocator, as CostReg does
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    elif not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError(f"workspace must be a contiguous CUDA tensor of at least {nbytes} bytes")
+    g_src = torch.empty((B, V, Cc, Hs, Ws), device=dev) if want_src_feat else None
+    g_hyp = torch.empty((B, D, Ht, Wt), device=dev) if want_depth_values else None
+    _lib.check(lib.gdb_feature_volume_backward(*(t.data_ptr() for t in args), B, V, Cc, Hs, Ws, D, Ht, Wt, int(bool(inv_depth)),
+                                               workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                               None if g_src is None else g_src.data_ptr(), None if g_hyp is None else g_hyp.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream))
+    return g_src, g_hyp
+
+
+def feature_volume_backward_workspace_bytes(B, V, Cc, Hs, Ws, D, Ht, Wt) -> Tuple[int, int]:
+    """(workspace bytes, fraction bits F of the fixed-point accumulators) of gdb_feature_volume_backward (host only)."""
+    n, f = C.c_size_t(), C.c_int32()
+    _lib.check(_lib.load().gdb_feature_volume_backward_workspace_bytes(B, V, Cc, Hs, Ws, D, Ht, Wt, C.byref(n), C.byref(f)))
+    return n.value, f.value
+
+
+class FeatureVolumeFunction(torch.autograd.Function):
+    """`build_feature_volume` with a backward: the forward is that call unchanged - the same bits - and the backward is
+    gdb_feature_volume_backward, to src_feat and depth_values only (the cameras get None), not differentiable again.
+    `FeatureVolumeFunction.apply(src_feat, src_exts, src_ints, tar_exts, tar_ints, depth_values, inv_depth)`."""
+
+    @staticmethod
+    def forward(ctx, src_feat, src_exts, src_ints, tar_exts, tar_ints, depth_values, inv_depth):
+        ctx.inv_depth = bool(inv_depth)
+        ctx.save_for_backward(src_feat, src_exts, src_ints, tar_exts, tar_ints, depth_values)
+        return build_feature_volume(src_feat, src_exts, src_ints, tar_exts, tar_ints, depth_values, inv_depth)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cost):
+        want_src, want_hyp = ctx.needs_input_grad[0], ctx.needs_input_grad[5]
+        if not (want_src or want_hyp):
+            return (None,) * 7
+        g_src, g_hyp = feature_volume_backward(*ctx.saved_tensors, g_cost, ctx.inv_depth, want_src, want_hyp)
+        return g_src, None, None, None, None, g_hyp, None
+
+
 def depth_regression(depth_values, depth_prob, ci_scale: float, inv_depth: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     lib = _lib.load()
     B, D, H, W = depth_values.shape
@@ -137,8 +195,9 @@ def cost_reg_train_layout(depth: int, cin: int, c: int, cout: int, B: int, D: in
 
 
 class _CostRegTrainFn(torch.autograd.Function):
-    """gdb_cost_reg_train / gdb_cost_reg_train_backward.  Inputs: the runner, the cost volume (no gradient is built for it) and the
-    parameters in `CostRegTrain.params()` order; the backward is not differentiable again."""
+    """gdb_cost_reg_train / gdb_cost_reg_train_backward.  Inputs: the runner, the cost volume and the parameters in
+    `CostRegTrain.params()` order; the backward is not differentiable again.  A cost volume that requires grad gets its gradient from
+    gdb_cost_reg_train_backward_cost; one that does not takes gdb_cost_reg_train_backward as before."""
 
     @staticmethod
     def forward(ctx, runner, cost, *params):
@@ -174,22 +233,32 @@ class _CostRegTrainFn(torch.autograd.Function):
         ws = torch.empty((ctx.ws_bytes,), dtype=torch.uint8, device=cost.device)
         grads = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in params]
         gptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-        _lib.check(lib.gdb_cost_reg_train_backward(runner.depth, runner.cin, runner.c, runner.cout, cost.data_ptr(), B, D, H, W,
-                                                   runner.param_pointers(params), None if g_volume is None else g_volume.data_ptr(),
-                                                   None if g_prob is None else g_prob.data_ptr(), saved.data_ptr(), ctx.saved_bytes,
-                                                   ws.data_ptr(), ctx.ws_bytes, gptrs, torch.cuda.current_stream(cost.device).cuda_stream))
-        return (None, None, *grads)
+        args = (runner.depth, runner.cin, runner.c, runner.cout, cost.data_ptr(), B, D, H, W,
+                runner.param_pointers(params), None if g_volume is None else g_volume.data_ptr(),
+                None if g_prob is None else g_prob.data_ptr(), saved.data_ptr(), ctx.saved_bytes, ws.data_ptr(), ctx.ws_bytes, gptrs)
+        stream = torch.cuda.current_stream(cost.device).cuda_stream
+        if not ctx.needs_input_grad[1]:
+            _lib.check(lib.gdb_cost_reg_train_backward(*args, stream))
+            return (None, None, *grads)
+        nbytes = C.c_size_t()
+        _lib.check(lib.gdb_cost_reg_train_cost_grad_bytes(runner.depth, runner.cin, runner.c, runner.cout, B, D, H, W, C.byref(nbytes)))
+        cws = torch.empty((nbytes.value,), dtype=torch.uint8, device=cost.device)
+        g_cost = torch.empty_like(cost)
+        _lib.check(lib.gdb_cost_reg_train_backward_cost(*args, g_cost.data_ptr(), cws.data_ptr(), nbytes.value, stream))
+        return (None, g_cost, *grads)
 
 
 class CostRegTrain:
     """Training-mode forward and backward of a `_UNet3d` on the HIP library: `CostRegTrain(module)(cost)` returns
     (volume, prob) like `module.train()(cost)`, updates the module's running statistics in place on the device and carries a graph
-    to the module's parameters.  The cost volume gets no gradient: one that requires grad is refused.  Nothing falls back: a plan or
+    to the module's parameters.  With `cost_grad` set a cost volume that requires grad is accepted and gets its gradient
+    (gdb_cost_reg_train_backward_cost); without it, as before, one that requires grad is refused.  Nothing falls back: a plan or
     shape the library refuses raises ValueError.  With `keep` set, `last` holds the latest call's saved buffer, its regions and the
     batch statistics (for inspection; off by default: it would pin the buffer until the next call)."""
 
-    def __init__(self, module: torch.nn.Module) -> None:
+    def __init__(self, module: torch.nn.Module, cost_grad: bool = False) -> None:
         self.module = module
+        self.cost_grad = bool(cost_grad)
         self.depth = int(module._depth)
         self.cin, self.c = int(module.conv0[0].in_channels), int(module.conv0[0].out_channels)
         self.cout = int(module.feat_head.out_channels)
@@ -223,8 +292,8 @@ class CostRegTrain:
         return (C.c_void_p * len(ptrs))(*ptrs)
 
     def __call__(self, cost: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        if cost.requires_grad:
-            raise ValueError("CostRegTrain builds no gradient for the cost volume: pass one that does not require grad")
+        if cost.requires_grad and not self.cost_grad:
+            raise ValueError("CostRegTrain builds the cost volume's gradient only with cost_grad set: pass one that does not require grad")
         cost = _c(cost, "cost")
         if cost.dim() != 5 or cost.shape[1] != self.cin:
             raise ValueError(f"cost volume of shape {tuple(cost.shape)}, expected (B, {self.cin}, D, H, W)")

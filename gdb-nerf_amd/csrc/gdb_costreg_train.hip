@@ -349,6 +349,23 @@ static void crt_dx_layer(const CrPlan& P, int li, CrLayer* d) {
     else cr_layer_set(*d, CR_S2, l.cout, l.cin, l.level_out, l.level_in, 0);
 }
 static size_t crt_packed_floats(const CrLayer& l) { return (size_t)l.nmt * l.taps * l.nchunk * 64 * l.e; }
+// the data gradient of conv0 - the cost volume's gradient - as a layer of the body: stride 1, flipped taps, roles swapped, base -> cin
+// channels, channel-last in and out; one plane per wave whatever cin (an 8-channel result fills half a 16-row tile)
+static void crt_dx0_layer(const CrPlan& P, CrLayer* d) {
+    cr_layer_set(*d, CR_S1, P.c, P.cin, 0, 0, 0);
+    d->zs = 1; d->taps = 27; d->rows = P.cin; d->nmt = (P.cin + 15) / 16;
+}
+// the scratch of the cost volume's gradient: conv0's repacked weights, then the gradient channel-last (B, D, H, W, cin)
+// (the weights stand at offset 0)
+struct CrtCostWs { size_t grad_off, total; };
+static CrtCostWs crt_cost_ws(const CrPlan& P, size_t nvox0) {
+    CrLayer d;
+    crt_dx0_layer(P, &d);
+    CrtCostWs w;
+    w.grad_off = (crt_packed_floats(d) * sizeof(float) + 255) / 256 * 256;
+    w.total = (w.grad_off + nvox0 * P.cin * sizeof(float) + 255) / 256 * 256;
+    return w;
+}
 
 static int crt_layout(const CrPlan& P, int B, int D, int H, int W, CrtLayout* L) {
     int rc = cr_check_shape(P, B, D, H, W);
@@ -438,12 +455,14 @@ static int crt_launch(const CrArgs& a, hipStream_t st) {
 static bool crt_conv_built(const CrLayer& l) {
     if (l.nc) return l.mode == CR_S1 && l.e == 4;
     if (l.mode == CR_S2) return l.zs == 1;
+    if (l.mode == CR_S1) return l.zs == 1;   // (E = 2: a stride-1 layer that reads 8 or 24 channels - conv0's data gradient)
     return l.e == 4 && l.zs == 1;
 }
 static int crt_conv(const CrLayer& l, const CrArgs& a, hipStream_t st) {
     if (l.nc) return l.zs == 2 ? crt_launch<CR_S1, 4, true, 2, CR_RAW>(a, st) : crt_launch<CR_S1, 4, true, 1, CR_RAW>(a, st);
     if (l.mode == CR_S2) return l.e == 4 ? crt_launch<CR_S2, 4, false, 1, CR_RAW>(a, st) : crt_launch<CR_S2, 2, false, 1, CR_RAW>(a, st);
-    return l.mode == CR_S1 ? crt_launch<CR_S1, 4, false, 1, CR_RAW>(a, st) : crt_launch<CR_UP, 4, false, 1, CR_RAW>(a, st);
+    if (l.mode == CR_S1) return l.e == 4 ? crt_launch<CR_S1, 4, false, 1, CR_RAW>(a, st) : crt_launch<CR_S1, 2, false, 1, CR_RAW>(a, st);
+    return crt_launch<CR_UP, 4, false, 1, CR_RAW>(a, st);
 }
 
 static int crt_pack(const CrLayer& l, const float* src, long long rs, long long cs, int flip, float* dst, hipStream_t st) {
@@ -587,10 +606,51 @@ extern "C" int gdb_cost_reg_train(int32_t depth, int32_t cin, int32_t base_chann
     return GDB_OK;
 }
 
+// channel-last (B, n, C) -> planar (B, C, n): one lane per output element
+__global__ void __launch_bounds__(256) k_crt_to_planar(const float* __restrict__ in, float* __restrict__ out, size_t n, int C, size_t total) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const size_t bc = t / n, p = t - bc * n, b = bc / C, c = bc - b * C;
+    out[t] = in[(b * n + p) * C + c];
+}
+
+extern "C" int gdb_cost_reg_train_cost_grad_bytes(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, int32_t B, int32_t D,
+                                                  int32_t H, int32_t W, size_t* out_bytes) {
+    CrPlan P;
+    int rc = cr_plan(depth, cin, base_channels, cout, &P);
+    if (rc != GDB_OK) return rc;
+    if (!out_bytes) return gdb_fail(GDB_E_BADARG, "out_bytes is NULL");
+    CrtLayout L;
+    if ((rc = crt_layout(P, B, D, H, W, &L)) != GDB_OK) return rc;
+    *out_bytes = crt_cost_ws(P, L.nvox[0]).total;
+    return GDB_OK;
+}
+
+static int crt_backward(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B,
+                        int32_t D, int32_t H, int32_t W, const void* const* d_params, const float* d_g_volume,
+                        const float* d_g_prob, const void* d_saved, size_t saved_bytes, void* d_ws, size_t ws_bytes,
+                        float* const* d_grads, float* d_g_cost, void* d_cost_ws, size_t cost_ws_bytes, void* stream_);
+
 extern "C" int gdb_cost_reg_train_backward(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B,
                                            int32_t D, int32_t H, int32_t W, const void* const* d_params, const float* d_g_volume,
                                            const float* d_g_prob, const void* d_saved, size_t saved_bytes, void* d_ws, size_t ws_bytes,
                                            float* const* d_grads, void* stream_) {
+    return crt_backward(depth, cin, base_channels, cout, d_cost, B, D, H, W, d_params, d_g_volume, d_g_prob, d_saved, saved_bytes, d_ws, ws_bytes,
+                        d_grads, nullptr, nullptr, 0, stream_);
+}
+
+extern "C" int gdb_cost_reg_train_backward_cost(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B,
+                                                int32_t D, int32_t H, int32_t W, const void* const* d_params, const float* d_g_volume,
+                                                const float* d_g_prob, const void* d_saved, size_t saved_bytes, void* d_ws, size_t ws_bytes,
+                                                float* const* d_grads, float* d_g_cost, void* d_cost_ws, size_t cost_ws_bytes, void* stream_) {
+    return crt_backward(depth, cin, base_channels, cout, d_cost, B, D, H, W, d_params, d_g_volume, d_g_prob, d_saved, saved_bytes, d_ws, ws_bytes,
+                        d_grads, d_g_cost, d_cost_ws, cost_ws_bytes, stream_);
+}
+
+static int crt_backward(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B,
+                        int32_t D, int32_t H, int32_t W, const void* const* d_params, const float* d_g_volume,
+                        const float* d_g_prob, const void* d_saved, size_t saved_bytes, void* d_ws, size_t ws_bytes,
+                        float* const* d_grads, float* d_g_cost, void* d_cost_ws, size_t cost_ws_bytes, void* stream_) {
     CrPlan P;
     int rc = cr_plan(depth, cin, base_channels, cout, &P);
     if (rc != GDB_OK) return rc;
@@ -611,6 +671,16 @@ extern "C" int gdb_cost_reg_train_backward(int32_t depth, int32_t cin, int32_t b
         crt_dx_layer(P, li, &DX[li]);
         if (!crt_conv_built(DX[li])) return gdb_fail(GDB_E_BADARG, "cost reg train: the data gradient of layer %d asks for a kernel that is not built", li);
         if ((rc = cr_geom(DX[li], B, D, H, W, &A[li])) != GDB_OK) return rc;
+    }
+    CrtCostWs CW = {};
+    if (d_g_cost) {   // the cost volume's gradient: conv0's data gradient, out of a scratch of its own
+        CW = crt_cost_ws(P, L.nvox[0]);
+        if (!d_cost_ws) return gdb_fail(GDB_E_BADARG, "cost reg train: the cost volume's gradient needs its scratch");
+        if (cost_ws_bytes < CW.total) return gdb_fail(GDB_E_WORKSPACE, "cost reg train: cost-gradient scratch of %zu bytes, %zu needed", cost_ws_bytes, CW.total);
+        crt_dx0_layer(P, &DX[0]);
+        if (!crt_conv_built(DX[0])) return gdb_fail(GDB_E_BADARG, "cost reg train: the data gradient of layer 0 asks for a kernel that is not built");
+        if ((rc = cr_geom(DX[0], B, D, H, W, &A[0])) != GDB_OK) return rc;
+        if (L.nvox[0] * (size_t)cin / 256 >= (1u << 31) - 1) return gdb_fail(GDB_E_SHAPE, "cost reg train: volume too large for the launch grid");
     }
     hipStream_t st = (hipStream_t)stream_;
     const char* sv = (const char*)d_saved;
@@ -673,7 +743,19 @@ extern "C" int gdb_cost_reg_train_backward(int32_t depth, int32_t cin, int32_t b
         if (l.mode == CR_UP) rc = crt_dw(P, li, L, B, D, H, W, in, 0, DZ[lo], 0, ws, d_grads[3 * li], st);
         else rc = crt_dw(P, li, L, B, D, H, W, DZ[lo], 0, in, li == 0, ws, d_grads[3 * li], st);
         if (rc != GDB_OK) return rc;
-        if (li == 0) break;   // the cost volume's gradient is not built
+        if (li == 0) {
+            if (!d_g_cost) break;   // the cost volume's gradient is not asked for
+            // row = input channel ci, k = output channel co of conv0's (co, ci, tap) weights, flipped; channel-last, then planar
+            float* p0 = (float*)d_cost_ws;
+            float* gcl = (float*)((char*)d_cost_ws + CW.grad_off);
+            if ((rc = crt_pack(DX[0], (const float*)d_params[0], 27, (long long)l.cin * 27, 1, p0, st)) != GDB_OK) return rc;
+            A[0].in = DZ[0]; A[0].out = gcl; A[0].skip = 0; A[0].w = p0; A[0].ep = nullptr;
+            if ((rc = crt_conv(DX[0], A[0], st)) != GDB_OK) return rc;
+            const size_t total = L.nvox[0] * (size_t)cin;
+            hipLaunchKernelGGL(k_crt_to_planar, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gcl, d_g_cost, L.nvox[0] / B, cin, total);
+            LAUNCH_CHECK("k_crt_to_planar");
+            break;
+        }
         const float* w = (const float*)d_params[6 * li];
         int skip = 0;
         if (l.mode == CR_S1) rc = crt_pack(DX[li], w, 27, (long long)l.cin * 27, 1, pdx, st);         // row = ci, k = co, flipped

@@ -65,6 +65,37 @@ struct HypTensor {
     }
 };
 
+// One view's warp of the voxel at pixel centre (px, py) and plane depth `depth`, stated ONCE for the sweep below and for its backward
+// (gdb_costvol_backward.hip), which must reproduce the coordinates, the floor, the tap indices and the weights bit for bit:
+//   q[r] = P[r][:3] . (px, py, 1),  p[r] = q[r] * depth + P[r][3]  (:466),  ix / iy the grid_sample pixel coordinates (:467-468),
+//   the x pair (xs, xs + 1) with weights (e0, e1) and the rows (ya, yb) with weights (ra, rb); zeros padding = weight 0, the
+//   indices are clamped into the map so every tap address exists.
+struct CostVolView { float q[3], p[3]; int x0, y0, xs, ya, yb; float fx, fy, e0, e1, ra, rb; bool finite; };
+__device__ __forceinline__ void costvol_view(const float* __restrict__ P, float px, float py, float depth, int Hs, int Ws, CostVolView& t) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        t.q[r] = P[4 * r] * px + P[4 * r + 1] * py + P[4 * r + 2];
+        t.p[r] = t.q[r] * depth + P[4 * r + 3];  // :466
+    }
+    float z = fmaxf(t.p[2], 1e-6f);
+    float gx = 2.f * (t.p[0] / z) / (float)Ws - 1.f, gy = 2.f * (t.p[1] / z) / (float)Hs - 1.f;   // :467-468
+    float ix = ((gx + 1.f) * (float)Ws - 1.f) / 2.f, iy = ((gy + 1.f) * (float)Hs - 1.f) / 2.f;
+    // keep far-away coordinates representable as int (they are outside anyway)
+    ix = fminf(fmaxf(ix, -4.f), (float)Ws + 4.f); iy = fminf(fmaxf(iy, -4.f), (float)Hs + 4.f);
+    t.finite = (t.p[0] == t.p[0]) && (t.p[1] == t.p[1]) && (t.p[2] == t.p[2]);
+    float xf = floorf(ix), yf = floorf(iy);
+    t.fx = ix - xf; t.fy = iy - yf;
+    t.x0 = (int)xf; t.y0 = (int)yf;
+    // x pair (xs, xs+1) covers columns x0, x0+1 where they exist
+    t.xs = min(max(t.x0, 0), Ws - 2);
+    float ea = (t.x0 >= 0 && t.x0 <= Ws - 1) ? 1.f - t.fx : 0.f, eb = (t.x0 + 1 >= 0 && t.x0 + 1 <= Ws - 1) ? t.fx : 0.f;
+    t.e0 = (t.x0 == t.xs ? ea : 0.f) + (t.x0 + 1 == t.xs ? eb : 0.f);
+    t.e1 = (t.x0 == t.xs + 1 ? ea : 0.f) + (t.x0 + 1 == t.xs + 1 ? eb : 0.f);
+    t.ra = (t.y0 >= 0 && t.y0 <= Hs - 1) ? 1.f - t.fy : 0.f; t.rb = (t.y0 + 1 >= 0 && t.y0 + 1 <= Hs - 1) ? t.fy : 0.f;
+    if (!t.finite) { t.e0 = t.e1 = 0.f; }
+    t.ya = min(max(t.y0, 0), Hs - 1); t.yb = min(max(t.y0 + 1, 0), Hs - 1);
+}
+
 // PAIR: a.feat is the channel-pair-interleaved copy (k_costvol_pairs; C even): per (row, view) ONE 16-byte load serves two channels.
 template <int VT, bool PAIR, class HYP>  // VT = number of source views: the per-view tap state lives in registers
 __device__ __forceinline__ void costvol_body(const CostVolArgs& a, const HYP& hyp) {
@@ -92,31 +123,10 @@ __device__ __forceinline__ void costvol_body(const CostVolArgs& a, const HYP& hy
     float w00[VT], w01[VT], w10[VT], w11[VT];
 #pragma unroll
     for (int v = 0; v < VT; ++v) {
-        {
-            const float* P = a.proj + ((size_t)b * a.V + v) * 12;
-            float p[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) p[r] = (P[4 * r] * px + P[4 * r + 1] * py + P[4 * r + 2]) * depth + P[4 * r + 3];  // :466
-            float z = fmaxf(p[2], 1e-6f);
-            float gx = 2.f * (p[0] / z) / (float)a.Ws - 1.f, gy = 2.f * (p[1] / z) / (float)a.Hs - 1.f;   // :467-468
-            float ix = ((gx + 1.f) * (float)a.Ws - 1.f) / 2.f, iy = ((gy + 1.f) * (float)a.Hs - 1.f) / 2.f;
-            // keep far-away coordinates representable as int (they are outside anyway)
-            ix = fminf(fmaxf(ix, -4.f), (float)a.Ws + 4.f); iy = fminf(fmaxf(iy, -4.f), (float)a.Hs + 4.f);
-            bool finite = (p[0] == p[0]) && (p[1] == p[1]) && (p[2] == p[2]);
-            float xf = floorf(ix), yf = floorf(iy);
-            float fx = ix - xf, fy = iy - yf;
-            int x0 = (int)xf, y0 = (int)yf;
-            // x pair (xs, xs+1) covers columns x0, x0+1 where they exist
-            int xs = min(max(x0, 0), a.Ws - 2);
-            float ea = (x0 >= 0 && x0 <= a.Ws - 1) ? 1.f - fx : 0.f, eb = (x0 + 1 >= 0 && x0 + 1 <= a.Ws - 1) ? fx : 0.f;
-            float e0 = (x0 == xs ? ea : 0.f) + (x0 + 1 == xs ? eb : 0.f);
-            float e1 = (x0 == xs + 1 ? ea : 0.f) + (x0 + 1 == xs + 1 ? eb : 0.f);
-            float ra = (y0 >= 0 && y0 <= a.Hs - 1) ? 1.f - fy : 0.f, rb = (y0 + 1 >= 0 && y0 + 1 <= a.Hs - 1) ? fy : 0.f;
-            if (!finite) { e0 = e1 = 0.f; }
-            int ya = min(max(y0, 0), a.Hs - 1), yb = min(max(y0 + 1, 0), a.Hs - 1);
-            off0[v] = (unsigned)(ya * a.Ws + xs); off1[v] = (unsigned)(yb * a.Ws + xs);
-            w00[v] = e0 * ra; w01[v] = e1 * ra; w10[v] = e0 * rb; w11[v] = e1 * rb;
-        }
+        CostVolView t;
+        costvol_view(a.proj + ((size_t)b * a.V + v) * 12, px, py, depth, a.Hs, a.Ws, t);
+        off0[v] = (unsigned)(t.ya * a.Ws + t.xs); off1[v] = (unsigned)(t.yb * a.Ws + t.xs);
+        w00[v] = t.e0 * t.ra; w01[v] = t.e1 * t.ra; w10[v] = t.e0 * t.rb; w11[v] = t.e1 * t.rb;
     }
     const size_t plane = (size_t)a.Hs * a.Ws, ovol = (size_t)a.D * a.Ht * a.Wt;
     const float invV = 1.f / (float)a.V;

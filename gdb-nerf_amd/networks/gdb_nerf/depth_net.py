@@ -201,6 +201,11 @@ class DepthNet(nn.Module):
         # and their backward from the HIP library (costvol.CostRegTrain); eval mode, CPU tensors and other dtypes are untouched
         self.hip_cost_reg_train = bool(getattr(mvs, "hip_cost_reg_train", False))
         self._hip_regs_train = {}   # stage -> costvol.CostRegTrain
+        # mvs.cost_volume_grad (default false): on fp32 CUDA tensors, while grad mode is on and the feature maps or the
+        # hypotheses require grad, the plane sweep runs inside costvol.FeatureVolumeFunction - the same forward call, the same bits -
+        # and its HIP backward carries the losses to feature_net and, under nerf.position_grad, to the previous stage's U-Net, as the
+        # PyTorch formulation does on the CPU.  Off, the HIP cost volume carries no graph.  mvs.hip_cascade stays eval-only.
+        self.cost_volume_grad = bool(getattr(mvs, "cost_volume_grad", False))
         # a whole stage as one library call (costvol.MvsStage): eval mode and fp32 CUDA inputs only; off by default
         self.hip_cascade = bool(getattr(mvs, "hip_cascade", False))
         # nerf.position_grad: the depth prior must carry a graph to the 3-D U-Nets.  Under that switch - and only while
@@ -289,7 +294,7 @@ class DepthNet(nn.Module):
         from ... import costvol
         reg = self._hip_regs_train.get(s)
         if reg is None or reg.module is not self.cost_regs[s]:
-            reg = self._hip_regs_train[s] = costvol.CostRegTrain(self.cost_regs[s])
+            reg = self._hip_regs_train[s] = costvol.CostRegTrain(self.cost_regs[s], cost_grad=self.cost_volume_grad)
         return reg
 
     def _cost_reg(self, s: int, cost: torch.Tensor, feats: torch.Tensor):
@@ -341,7 +346,10 @@ class DepthNet(nn.Module):
             if _use_hip(feats, self.hip_cost_volume):
                 from ... import costvol
                 hyp = hyp.contiguous()
-                cost = costvol.build_feature_volume(feats, src_exts, K_src, tar_exts, K_tar, hyp, self.inv_depth[s])
+                if self.cost_volume_grad and torch.is_grad_enabled() and (feats.requires_grad or hyp.requires_grad):
+                    cost = costvol.FeatureVolumeFunction.apply(feats, src_exts, K_src, tar_exts, K_tar, hyp, self.inv_depth[s])
+                else:
+                    cost = costvol.build_feature_volume(feats, src_exts, K_src, tar_exts, K_tar, hyp, self.inv_depth[s])
                 volume, prob = self._cost_reg(s, cost, feats)
                 if self.position_grad and torch.is_grad_enabled() and prob.requires_grad:
                     depth, search = HipDepthRegression.apply(hyp, prob, self.ci_scales[s], self.inv_depth[s])

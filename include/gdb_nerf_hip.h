@@ -469,6 +469,27 @@ int gdb_build_feature_volume_ws(const float* d_src_feat, const float* d_src_exts
                                 int32_t B, int32_t V, int32_t C, int32_t Hs, int32_t Ws, int32_t D, int32_t Ht, int32_t Wt,
                                 int32_t inv_depth, float* d_proj_ws, float* d_pair_ws, float* d_out, void* stream);
 
+/* Backward of gdb_build_feature_volume (additions to ABI v7): from the forward's inputs and the upstream d_g_cost
+ * (B,C,D,Ht,Wt) the gradients d_g_src_feat (B,V,C,Hs,Ws) and d_g_depth_values (B,D,Ht,Wt); either output may be NULL and is then
+ * skipped (both NULL: GDB_E_BADARG).  The cameras get no gradient.  Coordinates, tap indices and weights are the forward's own bits.
+ *   d_g_src_feat: d val_v = g (2/V)(val_v - mean), scattered through the forward's four tap weights (zeros padding), accumulated in
+ *     64-bit fixed point - contributions scaled by 2^(F - e), e = ceil(log2 max|g_cost|) + ceil(log2 max|src_feat|) + 2,
+ *     F = min(40, 62 - ceil(log2(4 D Ht Wt))), one integer atomic each, folded to float once: bit-identical from run to run.
+ *   d_g_depth_values: one owner per element, fixed order; through the perspective divide with clamp_min(1e-6)'s derivative, times
+ *     -1/h^2 under inv_depth; a view whose coordinate derivative is not finite adds nothing.
+ *   max|g_cost| == 0 or max|src_feat| == 0: exact zeros.  Either not finite: both outputs are NaN.
+ * Accepts every shape the forward accepts (V = 1 .. GDB_MAX_VIEWS, C >= 1, Ws >= 2, Hs >= 1); every refusal comes before the first
+ * launch.  d_workspace: gdb_feature_volume_backward_workspace_bytes bytes (contents on entry do not matter; a call without
+ * d_g_src_feat needs only 256 + 48 B V bytes rounded up to 256); a short one is GDB_E_WORKSPACE.  *out_frac_bits (may be NULL) = F.
+ * No host synchronisation, no process-global state. */
+int gdb_feature_volume_backward_workspace_bytes(int32_t B, int32_t V, int32_t C, int32_t Hs, int32_t Ws, int32_t D, int32_t Ht, int32_t Wt,
+                                                size_t* out_bytes, int32_t* out_frac_bits);
+int gdb_feature_volume_backward(const float* d_src_feat, const float* d_src_exts, const float* d_src_ints,
+                                const float* d_tar_exts, const float* d_tar_ints, const float* d_depth_values, const float* d_g_cost,
+                                int32_t B, int32_t V, int32_t C, int32_t Hs, int32_t Ws, int32_t D, int32_t Ht, int32_t Wt,
+                                int32_t inv_depth, void* d_workspace, size_t ws_bytes, float* d_g_src_feat, float* d_g_depth_values,
+                                void* stream);
+
 /* depth_regression, depth_net.py:479-514: d_depth (B,1,H,W) soft-argmax of d_depth_values (B,D,H,W) under
  * d_depth_prob, d_ci (B,2,H,W) = mean -/+ ci_scale*std clipped to the hypothesis range (both returned as
  * depths when inv_depth). */
@@ -900,6 +921,18 @@ int gdb_cost_reg_train_backward(int32_t depth, int32_t cin, int32_t base_channel
                                 int32_t H, int32_t W, const void* const* d_params, const float* d_g_volume, const float* d_g_prob,
                                 const void* d_saved, size_t saved_bytes, void* d_workspace, size_t ws_bytes, float* const* d_grads,
                                 void* stream);
+/* The same backward, handing back the cost volume's gradient as well (additions to ABI v7): d_g_cost (B, cin, D, H, W),
+ * planar like d_cost, = conv0's data gradient - the shared convolution body once more, stride 1, flipped taps, roles swapped, base ->
+ * cin channels - out of d_cost_workspace, gdb_cost_reg_train_cost_grad_bytes bytes of scratch of its own (conv0's repacked weights and
+ * the gradient channel-last; contents on entry do not matter; a short one is GDB_E_WORKSPACE, a NULL one GDB_E_BADARG).  With
+ * d_g_cost == NULL the scratch is not read and the work and the results are those of gdb_cost_reg_train_backward, bit for bit; with
+ * it, the parameter gradients are those same bits.  gdb_cost_reg_train_layout answers as before. */
+int gdb_cost_reg_train_cost_grad_bytes(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, int32_t B, int32_t D, int32_t H,
+                                       int32_t W, size_t* out_bytes);
+int gdb_cost_reg_train_backward_cost(int32_t depth, int32_t cin, int32_t base_channels, int32_t cout, const float* d_cost, int32_t B,
+                                     int32_t D, int32_t H, int32_t W, const void* const* d_params, const float* d_g_volume,
+                                     const float* d_g_prob, const void* d_saved, size_t saved_bytes, void* d_workspace, size_t ws_bytes,
+                                     float* const* d_grads, float* d_g_cost, void* d_cost_workspace, size_t cost_ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
