@@ -19,7 +19,9 @@ DEFAULTS = {
     "train": {"pretrain": "", "epoch": 10000, "num_workers": 8, "collator": "default", "batch_sampler": "default", "shuffle": True,
               "eps": 1.0e-8, "sampler_meta": {"input_views_num": [], "input_views_prob": []}, "optim": "adam", "lr": 5.0e-4,
               "weight_decay": 0.0, "scheduler": {"type": "multi_step", "milestones": [80, 120, 200, 240], "gamma": 0.5}, "batch_size": 4,
-              "hip_loss": False, "photometric_weights": [1.0, 0.1, 0.05], "vgg_weights": ""},
+              "hip_loss": False, "photometric_weights": [1.0, 0.1, 0.05], "vgg_weights": "",
+              # hip_optimizer: adam / adamw as optim.HipAdam - clip + step of every tensor in one library call (train/optimizer.py)
+              "hip_optimizer": False},
     "test": {"batch_size": 1, "collator": "default", "epoch": -1, "batch_sampler": "default",
              "sampler_meta": {"input_views_num": [], "input_views_prob": []}, "eval_depth": False, "eval_center": False,
              "hip_metrics": False, "lpips_weights": ""},

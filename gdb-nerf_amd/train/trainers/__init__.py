@@ -1,1 +1,1 @@
-from .make_trainer import make_wrapper  # noqa: F401
+from .make_trainer import make_trainer, make_wrapper  # noqa: F401

@@ -934,6 +934,27 @@ int gdb_cost_reg_train_backward_cost(int32_t depth, int32_t cin, int32_t base_ch
                                      const float* d_g_prob, const void* d_saved, size_t saved_bytes, void* d_workspace, size_t ws_bytes,
                                      float* const* d_grads, float* d_g_cost, void* d_cost_workspace, size_t cost_ws_bytes, void* stream);
 
+/* ---- the optimiser step: clip_grad_value_ + Adam / AdamW over n fp32 tensors in one call (addition to ABI v7)
+ * Every array argument is a HOST array with one entry per tensor: the four DEVICE pointers (parameter, gradient, exp_avg, exp_avg_sq,
+ * each numel[i] contiguous floats, 4-byte aligned at least; the four may not overlap), the element count, the tensor's own
+ * hyper-parameters as doubles, and its own step count t = step[i], ALREADY incremented (the first step passes 1).  clip_value <= 0
+ * means no clipping; decoupled != 0 is AdamW.  Per tensor the host forms, in double, 1 - beta1, 1 - beta2, 1 - lr weight_decay,
+ * step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) and rounds each to float once - what torch's single-tensor Adam does
+ * with a Python-number step.  Per element, in this order, each step one fp32 rounding (no fused multiply-add):
+ *   1. clip_value > 0:  g = g < -c ? -c : (g > c ? c : g), and the clamped value is WRITTEN BACK to the gradient, as clip_grad_value_
+ *      leaves it.  A NaN gradient stays NaN (torch.clamp), +-inf becomes +-c.  Without clipping the gradient is only read.
+ *   2. weight_decay != 0:  Adam (L2): g' = g + wd p (the stored gradient keeps the clamped g);  AdamW: p = p (1 - lr wd).
+ *   3. m = m + (g' - m)(1 - beta1);   v = v beta2;   v = v + (1 - beta2) g' g'.
+ *   4. denom = sqrt(v) / bc2_sqrt + eps;   p = p - step_size (m / denom).
+ * ceil(tensors / 48) launches on `stream`, each taking its tensors' pointers by value in the kernel arguments: no device-resident
+ * table, no workspace, no host synchronisation, no process-global state.  Every element is owned by one lane: two calls from the
+ * same state give the same bits.  Tensors with numel 0 take no part; n == 0 or all numel 0 is GDB_OK with no launch.
+ * Refused before anything is launched: n < 0, a NULL array, a NULL pointer among a tensor's four, step < 1, a beta outside [0, 1)
+ * (GDB_E_BADARG); numel < 0 or beyond 2^31 - 1 chunks of 2048 elements (GDB_E_SHAPE). */
+int gdb_adam_step(int32_t n, float* const* d_param, float* const* d_grad, float* const* d_exp_avg, float* const* d_exp_avg_sq,
+                  const int64_t* numel, const double* lr, const double* beta1, const double* beta2, const double* eps,
+                  const double* weight_decay, const int64_t* step, double clip_value, int32_t decoupled, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
