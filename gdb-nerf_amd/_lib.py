@@ -158,6 +158,14 @@ _SIGNATURES = {
                                                      C.POINTER(_P), _P, _P, C.c_size_t, _P]),
     "gdb_feature_volume_backward_workspace_bytes": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     "gdb_feature_volume_backward": (C.c_int, [_P] * 7 + [C.c_int32] * 9 + [_P, C.c_size_t, _P, _P, _P]),
+    "gdb_decoder_train_packed_floats": (C.c_int, [_CFG, C.c_int32, C.POINTER(C.c_size_t)]),
+    "gdb_decoder_train_pack": (C.c_int, [_CFG, C.c_int32, C.c_int32, C.POINTER(_P), _P, C.c_size_t, _P]),
+    "gdb_decoder_train_saved_bytes": (C.c_int, [_CFG, _FRM, C.c_int32, C.POINTER(C.c_size_t)]),
+    "gdb_decoder_train_layout": (C.c_int, [_CFG, _FRM, C.c_int32, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "gdb_decoder_train_forward": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
+    "gdb_decoder_train_backward_bytes": (C.c_int, [_CFG, _FRM, C.c_int32, C.POINTER(C.c_size_t)]),
+    "gdb_decoder_train_backward": (C.c_int, [_CFG, _FRM, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(_P), _P, C.c_size_t, _P, _P, C.c_size_t,
+                                             C.POINTER(_P), _P, C.c_int32, _P]),
     "gdb_adam_step": (C.c_int, [C.c_int32] + [C.POINTER(_P)] * 4 + [C.POINTER(C.c_int64)] + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_int64),
                                 C.c_double, C.c_int32, _P]),
 }

@@ -21,14 +21,14 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgdbnerf_hip.so")
 PEAKS_SRC = os.path.join(HERE, "..", "tools", "ubench", "peaks.hip")
 PEAKS_LIB = os.path.join(HERE, "libgdbpeaks.so")
-SOURCES = ("gdb_ops.hip", "gdb_mlp.hip", "gdb_fused.hip", "gdb_costvol.hip", "gdb_merge.hip", "gdb_decoder.hip", "gdb_decoder_f16.hip", "gdb_costreg.hip", "gdb_fpn.hip", "gdb_metrics.hip", "gdb_cascade.hip", "gdb_lpips.hip", "gdb_backward.hip", "gdb_encode_backward.hip", "gdb_position_backward.hip", "gdb_loss.hip", "gdb_stage_nerf.hip", "gdb_costreg_train.hip", "gdb_costvol_backward.hip", "gdb_optim.hip")
+SOURCES = ("gdb_ops.hip", "gdb_mlp.hip", "gdb_fused.hip", "gdb_costvol.hip", "gdb_merge.hip", "gdb_decoder.hip", "gdb_decoder_f16.hip", "gdb_costreg.hip", "gdb_fpn.hip", "gdb_metrics.hip", "gdb_cascade.hip", "gdb_lpips.hip", "gdb_backward.hip", "gdb_encode_backward.hip", "gdb_position_backward.hip", "gdb_loss.hip", "gdb_stage_nerf.hip", "gdb_costreg_train.hip", "gdb_costvol_backward.hip", "gdb_optim.hip", "gdb_decoder_train.hip")
 # -fno-slp-vectorize: packed f32 VALU (v_pk_*_f32) beside MFMAs is an anti-lever on gfx950 (MI355X_MICROARCH.md,
 # "price of one filler beside MFMAs": +22..26 cycles per packed op) and hipcc's SLP pass packs adjacent f32 mul/add
 # under plain -O3; DESIGN.md §4.1 has the history of the stale-lane corruption first seen with it.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function"]
 # The operator mirrors keep a*b+c as two roundings (as separate torch ops are) unless written fmaf();
 # the fused fast path lets the compiler contract.
-CONTRACT = {"gdb_ops.hip": "off", "gdb_mlp.hip": "off", "gdb_fused.hip": "fast-honor-pragmas", "gdb_costvol.hip": "off", "gdb_merge.hip": "off", "gdb_decoder.hip": "off", "gdb_decoder_f16.hip": "off", "gdb_costreg.hip": "off", "gdb_fpn.hip": "off", "gdb_metrics.hip": "off", "gdb_cascade.hip": "off", "gdb_lpips.hip": "off", "gdb_backward.hip": "off", "gdb_encode_backward.hip": "off", "gdb_position_backward.hip": "off", "gdb_loss.hip": "off", "gdb_stage_nerf.hip": "off", "gdb_costreg_train.hip": "off", "gdb_costvol_backward.hip": "off", "gdb_optim.hip": "off"}
+CONTRACT = {"gdb_ops.hip": "off", "gdb_mlp.hip": "off", "gdb_fused.hip": "fast-honor-pragmas", "gdb_costvol.hip": "off", "gdb_merge.hip": "off", "gdb_decoder.hip": "off", "gdb_decoder_f16.hip": "off", "gdb_costreg.hip": "off", "gdb_fpn.hip": "off", "gdb_metrics.hip": "off", "gdb_cascade.hip": "off", "gdb_lpips.hip": "off", "gdb_backward.hip": "off", "gdb_encode_backward.hip": "off", "gdb_position_backward.hip": "off", "gdb_loss.hip": "off", "gdb_stage_nerf.hip": "off", "gdb_costreg_train.hip": "off", "gdb_costvol_backward.hip": "off", "gdb_optim.hip": "off", "gdb_decoder_train.hip": "off"}
 
 
 # Kernels that must not touch private memory at all (no vector spill, no struct parked in scratch).  The round-1 "packed f32"

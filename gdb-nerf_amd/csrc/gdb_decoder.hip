@@ -26,6 +26,7 @@
 //   pattern: deterministic), and x += x3 * gate (+ the global residual at the end) happens while the NEXT convolution stages its
 //   input (Stager<FUSE>).
 #include "gdb_internal.h"
+#include "gdb_decoder_layout.h"
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -39,56 +40,7 @@ typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef unsigned U2 __attribute__((ext_vector_type(2)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 
-#define DEC_NF 64    // num_feats (network.py:51)
-#define DEC_G 32     // growth rate (decoder_rdn.py:27)
-#define DEC_PX 34    // pixels per staged row: 32 + halo
-#define DEC_CHS 34   // floats per staged pixel: 32 channels of the chunk + 2 (bank spread for the 8-byte reads)
-#define DECX_PXD 20  // split-f16 staging: dwords per pixel = 8 (hi halves of a chunk's 16 channels) + 8 (lo halves) + 4 (bank spread for the 16-byte reads)
-#define DEC_SE_R 4   // SE bottleneck: 64 / 16
-
-// ---- packed weights -------------------------------------------------------------------------------------------------
-// conv_floats(cin, nt): floats of a packed layer of 32 nt output channels (fp32 form pack_conv16 and split-f16 form pack_conv_x alike).
-static size_t conv_floats(int cin, int nt) { return (size_t)((cin + 31) / 32) * 9 * 8 * 64 * 2 * nt; }
-#define DEC_MAX_LAYERS 16   // dense blocks (decoder_rdn.py:57 takes any count; every config of the reference has 3)
-struct DecLayout {
-    size_t in_w, in_b, blk[DEC_MAX_LAYERS][5] /* conv1, conv2, conv3, fc0, fc2 */, up_w, up_b;
-    size_t in_wx, blkx[DEC_MAX_LAYERS][3], up_wx;  // the same convolutions as split-f16 fragments (pack_conv_x), behind the fp32 ones
-    // upscale_factor 4 (bundle_size 4: two up stages, decoder_rdn.py:59-62): the FIRST stage's 64 -> 256 convolution as four 64 -> 64
-    // convolutions, one per sub-pixel of its PixelShuffle (fp32 and split-f16 forms, biases); up_w / up_b then hold the SECOND stage folded
-    // with out_conv.  Zero-sized at upscale_factor 2.
-    size_t u1_w[4], u1_wx[4], u1_b[4];
-    size_t total;
-};
-static DecLayout dec_layout(int nlayers, int bundle_size = 2) {
-    DecLayout L{};
-    size_t o = 0;
-    L.in_w = o; o += conv_floats(27, 2);
-    L.in_b = o; o += 64;
-    for (int b = 0; b < nlayers; ++b) {
-        L.blk[b][0] = o; o += conv_floats(64, 1);
-        L.blk[b][1] = o; o += conv_floats(96, 1);
-        L.blk[b][2] = o; o += conv_floats(128, 2);
-        L.blk[b][3] = o; o += DEC_SE_R * DEC_NF;
-        L.blk[b][4] = o; o += DEC_NF * DEC_SE_R;
-    }
-    L.up_w = o; o += conv_floats(64, 1);
-    L.up_b = o; o += 32;
-    L.in_wx = o; o += conv_floats(27, 2);
-    for (int b = 0; b < nlayers; ++b) {
-        L.blkx[b][0] = o; o += conv_floats(64, 1);
-        L.blkx[b][1] = o; o += conv_floats(96, 1);
-        L.blkx[b][2] = o; o += conv_floats(128, 2);
-    }
-    L.up_wx = o; o += conv_floats(64, 1);
-    if (bundle_size == 4)
-        for (int sp = 0; sp < 4; ++sp) {
-            L.u1_w[sp] = o; o += conv_floats(64, 2);
-            L.u1_wx[sp] = o; o += conv_floats(64, 2);
-            L.u1_b[sp] = o; o += 64;
-        }
-    L.total = (o + 8 * 128 + 63) / 64 * 64;  // + one tap block: the fp32 conv kernel's weight prefetch runs one tap ahead
-    return L;
-}
+// DEC_NF .. DEC_SE_R, conv_floats, DecLayout / dec_layout, DecBufs: gdb_decoder_layout.h (shared with gdb_decoder_train.hip)
 // w: (cout, cin, 3, 3) row-major as torch stores it
 // A layer for k_conv16 (v_mfma_f32_16x16x4_f32: 16 output rows x 16 pixels x 4 input channels per instruction, the same FLOP rate
 // as the 32x32x2 form): [tile mt][32-channel chunk][tap 9][g4 2][lane 64][4] floats; element e of lane l =
@@ -249,24 +201,7 @@ extern "C" int gdb_decoder_workspace_bytes(const GdbConfig* cfg, const GdbFrame*
 }
 
 // ---- 3x3 convolution ----------------------------------------------------------------------------------------------------
-struct ConvArgs {
-    const float* in; int in_stride, in_off, cin, nchunk, vec;  // vec: the input rows allow 16-byte loads
-    const float* in2; int split;    // 32-channel chunks >= split come from in2 (row stride in_stride, channel 32 (chunk - split))
-    const float* w; const float* bias;
-    float* out; int out_stride, out_off, cout, relu;
-    float* rgb;                     // folded up stage: (B,3,2H,2W) NCHW, channel c = 3 s + o of sub-pixel s = dy*2 + dx
-    int up2, up_dy, up_dx;          // first up stage of upscale_factor 4: output pixel (y, x) is written at (2y + up_dy, 2x + up_dx) of a (2H, 2W) map
-    // squeeze-excitation folded into the consumer (FUSE kernels; decoder_rdn.py:40,78): the staged input is x = in + fT * gate (+ fS),
-    // all (pixels, 64); the workgroup's own pixels of x are also written to fX (the next block's P) when fX is set
-    const float* fT; const float* fgate; const float* fS; float* fX;
-    float* se_part;                 // SEP kernels (conv3): channel sums of the output per (row, 32-pixel segment)
-    unsigned* zero;                 // in_conv: the arrival counters of k_se_gate, cleared for this decode
-    int B, H, W, tilesX, tilesY;
-    // row window (gdb_decode_rows): the map the kernel runs on is rows [wy0, wy0 + H) of a frame of Hf rows.  `in` holds in_H rows per
-    // batch item starting at row in_y0 (in_conv reads the frame-sized bundle rows in place; every other input is window-sized); se_part
-    // is frame-sized and receives - like rgb - the rows [own0, own1) of the frame only.  The whole-frame decode: 0, H, H, 0, 0, H.
-    int wy0, Hf, in_H, in_y0, own0, own1;
-};
+// ConvArgs: gdb_decoder_layout.h
 
 extern __shared__ float dsmem[];
 
@@ -910,17 +845,27 @@ static int dec_split_attrs() {
 // p > 0 first runs block p-1's squeeze-excitation gate on the frame-sized `part`; p < L then runs block p's three convolutions (in_conv
 // first when p = 0); p = L runs the up stage(s) into d_rgb_c.  Phases 0 .. L in a row are gdb_decode's launch sequence.
 static int dec_phases(const GdbConfig* cfg, int B, int H, int W, const float* d_bundle_feat, int ld_bundle_feat, const float* d_packed,
-                      int num_layers, bool split, int r0, int r1, int w0, int w1, int ph0, int ph1, void* d_ws, float* d_rgb_c, hipStream_t st) {
+                      int num_layers, bool split, int r0, int r1, int w0, int w1, int ph0, int ph1, void* d_ws, float* d_rgb_c, hipStream_t st,
+                      const DecBufs* bufs = nullptr) {
     const int Q = 3 * cfg->bundle_size * cfg->bundle_size + GDB_CFR + GDB_CV, n_rgb = 3 * cfg->bundle_size * cfg->bundle_size;
     const bool up4 = cfg->bundle_size == 4;
     const int Hw = w1 - w0;
     const DecWs ws = dec_ws(B, Hw, W, cfg->bundle_size, H);
     const DecLayout L = dec_layout(num_layers, cfg->bundle_size);
-    float* Pbuf[3] = {(float*)((char*)d_ws + ws.P[0]), (float*)((char*)d_ws + ws.P[1]), (float*)((char*)d_ws + ws.P[2])};
-    auto Px = [&](int b) -> float* { return b == 0 ? Pbuf[0] : Pbuf[1 + ((b - 1) & 1)]; };   // the input x of dense block b
-    float* Y = (float*)((char*)d_ws + ws.Y); float* T = (float*)((char*)d_ws + ws.T);
-    float* part = (float*)((char*)d_ws + ws.part); float* part2 = (float*)((char*)d_ws + ws.part2);
-    float* gate = (float*)((char*)d_ws + ws.gate); unsigned* count = (unsigned*)((char*)d_ws + ws.count);
+    // the buffers of the decode: the caller's (the training forward: every block its own), or the rotating ones of the workspace
+    DecBufs own{};
+    if (!bufs) {
+        float* Pbuf[3] = {(float*)((char*)d_ws + ws.P[0]), (float*)((char*)d_ws + ws.P[1]), (float*)((char*)d_ws + ws.P[2])};
+        for (int b = 0; b < num_layers; ++b) {
+            own.x[b] = b == 0 ? Pbuf[0] : Pbuf[1 + ((b - 1) & 1)];
+            own.ab[b] = (float*)((char*)d_ws + ws.Y); own.T[b] = (float*)((char*)d_ws + ws.T); own.gate[b] = (float*)((char*)d_ws + ws.gate);
+        }
+        own.part = (float*)((char*)d_ws + ws.part); own.part2 = (float*)((char*)d_ws + ws.part2);
+        own.count = (unsigned*)((char*)d_ws + ws.count);
+        bufs = &own;
+    }
+    auto Px = [&](int b) -> float* { return bufs->x[b]; };   // the input x of dense block b
+    float* part = bufs->part; float* part2 = bufs->part2; unsigned* count = bufs->count;
     // the map the next convolution runs on: window rows, its frame row origin, the frame's rows, the rows owned (all doubled for the
     // last stage of upscale_factor 4, which runs on (2H, 2W))
     int cH = Hw, cW = W, cy0 = w0, cHf = H, co0 = r0, co1 = r1;
@@ -946,7 +891,7 @@ static int dec_phases(const GdbConfig* cfg, int B, int H, int W, const float* d_
         if (ph > 0) {   // squeeze-excitation of block ph-1 on the frame's channel sums   decoder_rdn.py:17-21
             const int b = ph - 1;
             hipLaunchKernelGGL(k_se_gate, dim3((unsigned)(B * ws.ngrp)), dim3(256), 0, st, part, ws.nseg, ws.ngrp, 1.f / (float)((size_t)H * W),
-                               d_packed + L.blk[b][3], d_packed + L.blk[b][4], part2, count, gate);
+                               d_packed + L.blk[b][3], d_packed + L.blk[b][4], part2, count, bufs->gate[b]);
             CK(hipGetLastError());
         }
         if (ph == 0) {   // shallow = in_conv(bundle channels n_rgb..Q-1)   decoder_rdn.py:76: block 0's x, and the global residual at the end
@@ -959,17 +904,17 @@ static int dec_phases(const GdbConfig* cfg, int B, int H, int W, const float* d_
         if (ph < num_layers) {   // ResidualDenseBlock.forward   decoder_rdn.py:35-41 (its gate: the next phase)
             const int b = ph;
             ConvArgs a{};
-            a.in_stride = DEC_NF; a.in_off = 0; a.out = Y; a.out_stride = DEC_NF; a.relu = 1;
+            a.in_stride = DEC_NF; a.in_off = 0; a.out = bufs->ab[b]; a.out_stride = DEC_NF; a.relu = 1;
             // conv1; from the second block on it first forms its own input x_b = x_{b-1} + x3_{b-1} * gate_{b-1} (:40) and leaves it in P[b]
             a.in = b ? Px(b - 1) : Px(0);
-            if (b) { a.fT = T; a.fgate = gate; a.fX = Px(b); }
+            if (b) { a.fT = bufs->T[b - 1]; a.fgate = bufs->gate[b - 1]; a.fX = Px(b); }
             a.cin = DEC_NF; a.w = d_packed + (split ? L.blkx[b][0] : L.blk[b][0]); a.out_off = 0; a.cout = DEC_G;
             CK(conv(a, 1));
             a.fT = nullptr; a.fgate = nullptr; a.fX = nullptr;
-            a.in = Px(b); a.in2 = Y; a.split = 2;
+            a.in = Px(b); a.in2 = bufs->ab[b]; a.split = 2;
             a.cin = DEC_NF + DEC_G; a.w = d_packed + (split ? L.blkx[b][1] : L.blk[b][1]); a.out_off = DEC_G;
             CK(conv(a, 1));
-            a.cin = DEC_NF + 2 * DEC_G; a.w = d_packed + (split ? L.blkx[b][2] : L.blk[b][2]); a.out = T; a.out_off = 0; a.cout = DEC_NF; a.relu = 0;
+            a.cin = DEC_NF + 2 * DEC_G; a.w = d_packed + (split ? L.blkx[b][2] : L.blk[b][2]); a.out = bufs->T[b]; a.out_off = 0; a.cout = DEC_NF; a.relu = 0;
             a.se_part = part;
             CK(conv(a, 2));
             continue;
@@ -977,7 +922,7 @@ static int dec_phases(const GdbConfig* cfg, int B, int H, int W, const float* d_
         if (!up4) {   // out_conv(PixelShuffle(up(x + shallow))) as one folded 64 -> 12 convolution on x = x_{L-1} + x3 * gate + shallow   :40,78-80
             ConvArgs a{};
             a.in = Px(num_layers - 1); a.in_stride = DEC_NF; a.in_off = 0; a.cin = DEC_NF;
-            a.fT = T; a.fgate = gate; a.fS = Px(0);
+            a.fT = bufs->T[num_layers - 1]; a.fgate = bufs->gate[num_layers - 1]; a.fS = Px(0); a.fX = bufs->xu;
             a.w = d_packed + (split ? L.up_wx : L.up_w); a.bias = d_packed + L.up_b;
             a.cout = 12; a.relu = 0; a.rgb = d_rgb_c;
             CK(conv(a, 1));
@@ -987,7 +932,8 @@ static int dec_phases(const GdbConfig* cfg, int B, int H, int W, const float* d_
             // out_conv as ONE 64 -> 12 convolution on U, written pixel-shuffled to the (4H, 4W) image - no non-linearity anywhere in between.
             float* X = (float*)((char*)d_ws + ws.X); float* U = (float*)((char*)d_ws + ws.U);
             const size_t npix = (size_t)Hw * W;
-            hipLaunchKernelGGL(k_apply_gate, dim3((unsigned)(((size_t)B * npix * 16 + 255) / 256)), dim3(256), 0, st, Px(num_layers - 1), T, gate, Px(0), X, npix, B);
+            hipLaunchKernelGGL(k_apply_gate, dim3((unsigned)(((size_t)B * npix * 16 + 255) / 256)), dim3(256), 0, st, Px(num_layers - 1), bufs->T[num_layers - 1],
+                               bufs->gate[num_layers - 1], Px(0), X, npix, B);
             CK(hipGetLastError());
             for (int sp = 0; sp < 4; ++sp) {
                 ConvArgs a{};
@@ -1007,6 +953,27 @@ static int dec_phases(const GdbConfig* cfg, int B, int H, int W, const float* d_
     }
 #undef CK
     return GDB_OK;
+}
+
+// gdb_decoder_train.hip: ONE fp32 convolution of a whole frame on k_conv16 - the data gradients are forward convolutions with the
+// channel roles swapped and the taps flipped (their weights packed that way).  The caller sets the operands (in, in_stride, in_off, cin,
+// in2 / split, w, bias, out, out_stride, out_off, cout, relu); the geometry is filled in here as dec_phases' `conv` does for the frame.
+int gdb_dec_conv_on(ConvArgs a, int B, int H, int W, hipStream_t st) {
+    a.B = B; a.H = H; a.W = W; a.tilesX = (W + 31) / 32; a.tilesY = (H + 1) / 2;
+    a.wy0 = 0; a.Hf = H; a.own0 = 0; a.own1 = H; a.in_H = H; a.in_y0 = 0;
+    a.nchunk = (a.cin + 31) / 32;
+    if (!a.in2) a.split = a.nchunk;
+    a.vec = (a.in_stride % 4 == 0) && (a.in_off % 4 == 0) && (a.cin % 4 == 0) && ((uintptr_t)a.in % 16 == 0);
+    const hipError_t e = a.cout > 32 ? launch_conv(a, st) : (a.cout > 16 ? launch_conv16<2>(a, st) : launch_conv16<1>(a, st));
+    if (e != hipSuccess) return gdb_fail(GDB_E_HIP, "decoder launch: %s", hipGetErrorString(e));
+    return GDB_OK;
+}
+
+// gdb_decoder_train.hip: the whole-frame fp32 sequence on buffers of the caller's (arguments checked there).
+int gdb_dec_phases_on(const GdbConfig* cfg, int B, int H, int W, const float* d_bundle_feat, int ld_bundle_feat, const float* d_packed,
+                      int num_layers, const DecBufs& bufs, float* d_rgb_c, hipStream_t st) {
+    return dec_phases(cfg, B, H, W, d_bundle_feat, ld_bundle_feat, d_packed, num_layers, false, 0, H, 0, H, 0, num_layers, nullptr, d_rgb_c, st,
+                      &bufs);
 }
 
 extern "C" int gdb_decode(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,

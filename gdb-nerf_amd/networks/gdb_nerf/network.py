@@ -18,6 +18,9 @@ What is differentiable:
     differentiable (`gdb_sample_backward`, `gdb_encode_position_backward`), so the colour loss - and `nerf_depth`,
     through `z_vals` - reaches `depth_net.*` through `depth_range` / `vol_range`: the depth prior moves the samples, as in the
     reference.  The cameras, the source images and `near_far` get no gradient.
+  * `nerf.hip_decoder_train: true` (with `hot_path: "mirrors"`, bundle_size 2; default false): in train mode with grad mode on the
+    decoder runs on the HIP library with a HIP backward (`decoder_train.DecodeTrainFunction`) instead of the PyTorch
+    module under autograd; eval mode and no_grad keep the module.
   * `hot_path: "fused"` is unchanged and non-differentiable: its outputs have no `grad_fn` whatever `requires_grad` says.
   * `mvs.stage_render: true` (training mode; independent of the hot path): `blend_rgbs` holds the depth net's stage images, whose loss
     reaches `depth_net.nerfs.*`, `depth_net.cost_regs[i]` through the stage's feature volume and `feature_net.*` through the gathered
@@ -71,6 +74,18 @@ class Network(nn.Module):
         if self.position_grad and getattr(nrf, "hot_path", "fused") != "mirrors":
             raise ValueError(f"nerf.position_grad needs nerf.hot_path 'mirrors' (got {getattr(nrf, 'hot_path', 'fused')!r}): the fused hot path is not differentiable")
         self.sampler = BundleSampler(self.global_num_depth, self.max_mipmap_level, encode_grad=self.encode_grad, position_grad=self.position_grad)
+        # nerf.hip_decoder_train: the decoder of the differentiable path on the HIP library with a HIP backward (DESIGN.md 4.23:
+        # decoder_train.DecodeTrainFunction) instead of the PyTorch module under autograd.  Needs the operator mirrors (the fused hot
+        # path carries no graph), bundle_size 2 and dec_layers 1 .. 16: anything else raises here, with the offending value.
+        self.hip_decoder_train = bool(getattr(nrf, "hip_decoder_train", False))
+        if self.hip_decoder_train:
+            if getattr(nrf, "hot_path", "fused") != "mirrors":
+                raise ValueError(f"nerf.hip_decoder_train needs nerf.hot_path 'mirrors' (got {getattr(nrf, 'hot_path', 'fused')!r}): the fused hot path is not differentiable")
+            if self.b_size != 2:
+                raise ValueError(f"nerf.hip_decoder_train is built for nerf.bundle_size 2 (got {self.b_size})")
+            if not 1 <= int(nrf.dec_layers) <= 16:
+                raise ValueError(f"nerf.hip_decoder_train is built for nerf.dec_layers 1..16 (got {nrf.dec_layers})")
+        self._decoder_train = None
 
         # pyramid level whose scale is closest to (not below) the bundle map's 1/b   (reference :40-43)
         self.feat_level = next((i for i, s in enumerate(fpn.feat_scales) if s >= 1.0 / self.b_size), len(fpn.feat_scales))
@@ -252,6 +267,16 @@ class Network(nn.Module):
             depth = 1.0 / depth
         return feat, depth, opacity
 
+    def _decoder_train_applies(self, bundle_feat: torch.Tensor) -> bool:
+        """nerf.hip_decoder_train takes the decoder of this forward: the switch is on, the module trains, grad mode is on, the rows or a
+        decoder parameter require grad, and everything is fp32 on a GPU.  Otherwise the PyTorch module runs as it always did."""
+        if not (self.hip_decoder_train and self.training and torch.is_grad_enabled()):
+            return False
+        ps = list(self.upsampler.parameters())
+        if not (bundle_feat.requires_grad or any(p.requires_grad for p in ps)):
+            return False
+        return all(t.is_cuda and t.dtype == torch.float32 for t in (bundle_feat, *ps))
+
     def forward(self, batch: Dict[str, Any]) -> Tuple[Dict[str, torch.Tensor], List[torch.Tensor], List[torch.Tensor]]:
         src, tar = batch["src_views"], batch["tar_views"]
         near_far = batch["near_far"]
@@ -322,7 +347,13 @@ class Network(nn.Module):
 
         nerf_feat = bundle_feat.view(B, H, W, -1).permute(0, 3, 1, 2)
         n_rgb = 3 * b * b
-        rgb_c = self.upsampler(nerf_feat[:, n_rgb:])
+        if self._decoder_train_applies(bundle_feat):
+            from ...decoder_train import DecodeTrainFunction, DecoderTrain, decoder_params
+            if self._decoder_train is None:
+                self._decoder_train = DecoderTrain(self.upsampler, self.b_size)
+            rgb_c = DecodeTrainFunction.apply(self._decoder_train, bundle_feat.contiguous(), B, H, W, *decoder_params(self.upsampler))
+        else:
+            rgb_c = self.upsampler(nerf_feat[:, n_rgb:])
         rgb_f = F.pixel_shuffle(nerf_feat[:, :n_rgb], b)
         up = lambda t: F.interpolate(t.view(B, 1, H, W), scale_factor=b, mode="bilinear", align_corners=False).squeeze(1)
         img = rgb_c + rgb_f

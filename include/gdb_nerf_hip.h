@@ -585,6 +585,44 @@ typedef struct GdbDecRegion {
 int gdb_decoder_rows_regions(const GdbConfig* cfg, const GdbFrame* shape, int32_t row_begin, int32_t row_end, int32_t num_layers,
                              GdbDecRegion* out, int32_t capacity, int32_t* out_count, int32_t* block_input);
 
+/* ---- the decoder in training mode: device-side pack, saved-activation forward, backward (ABI v7, added) ---------- */
+/* fp32 only (precision must be GDB_PREC_F32), bundle_size 2, num_layers 1 .. 16, B <= 256, whole frames: every entry refuses anything
+ * else.
+ *
+ * gdb_decoder_train_pack: d_tensors = DEVICE pointers to the parameters in the state-dict order of gdb_pack_decoder_weights
+ * (2 + 5 num_layers + 4).  Two launches on `stream` write d_packed (gdb_decoder_train_packed_floats floats): the fp32 operand forms at
+ * the offsets of the eval-mode packed buffer's fp32 sections, byte for byte what gdb_pack_decoder_weights writes from the same values
+ * (the last up stage folded with out_conv in double, in the host's order, rounded once), then a zeroed tap block, then the
+ * data-gradient forms the backward's convolutions read (channel roles swapped, taps flipped).  No parameter is copied
+ * to the host and nothing synchronises.  gdb_decode(GDB_PREC_F32) accepts the buffer too; the split-f16 forms are not in it.
+ *
+ * gdb_decoder_train_forward: gdb_decode's fp32 launch sequence with every block's activations kept in d_saved
+ * (gdb_decoder_train_saved_bytes): d_rgb_c (B,3,2H,2W) is bit-identical to gdb_decode(..., GDB_PREC_F32, ...) on the same inputs.
+ * gdb_decoder_train_layout (host only) names the regions, 4 num_layers + 3 of them: per block b "x.<b>" (its input, (B, H, W, 64);
+ * x.0 = shallow = in_conv's output), "ab.<b>" ([a | b] = conv1 | conv2 after ReLU, 32 + 32 channels), "T.<b>" (conv3's output),
+ * "gate.<b>" ((B, 64)); then "xu" (the up stage's input x_L + shallow, x_L = x_{L-1} + T gate), "part" ((B, H, ceil(W/32), 64): the last
+ * block's channel sums of T per row and 32-pixel segment) and "part2" ((B, groups, 64)).  out may be NULL to query *out_count. */
+int gdb_decoder_train_packed_floats(const GdbConfig* cfg, int32_t num_layers, size_t* out_floats);
+int gdb_decoder_train_pack(const GdbConfig* cfg, int32_t num_layers, int32_t precision, const float* const* d_tensors, float* d_packed,
+                           size_t packed_floats, void* stream);
+int gdb_decoder_train_saved_bytes(const GdbConfig* cfg, const GdbFrame* shape, int32_t num_layers, size_t* out_bytes);
+int gdb_decoder_train_layout(const GdbConfig* cfg, const GdbFrame* shape, int32_t num_layers, GdbDecRegion* out, int32_t capacity,
+                             int32_t* out_count);
+int gdb_decoder_train_forward(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
+                              const float* d_packed, int32_t num_layers, int32_t precision, void* d_saved, size_t saved_bytes,
+                              float* d_rgb_c, void* stream);
+/* gdb_decoder_train_backward: from d_g_rgb_c (B,3,2H,2W), the saved buffer of the forward on the same rows and packed weights, and
+ * the parameters themselves (d_tensors, as for the pack: the fold's backward reads up.0 and out_conv), the gradient of every parameter
+ * in that parameter's own layout - d_grads: 2 + 5 num_layers + 4 device pointers in state-dict order, any of them NULL (or d_grads
+ * NULL) - and of the bundle rows: d_g_rows (B H W, ld_g_rows >= Q), columns 12 .. 38 the gradient, 0 .. 11 written as zero, columns
+ * from 39 on left alone; may be NULL.  Everything is overwritten, not accumulated.  d_workspace: gdb_decoder_train_backward_bytes,
+ * caller-owned scratch.  No atomics on data: two runs are bit-identical. */
+int gdb_decoder_train_backward_bytes(const GdbConfig* cfg, const GdbFrame* shape, int32_t num_layers, size_t* out_bytes);
+int gdb_decoder_train_backward(const GdbConfig* cfg, const GdbFrame* shape, const float* d_bundle_feat, int32_t ld_bundle_feat,
+                               const float* d_packed, int32_t num_layers, int32_t precision, const float* const* d_tensors,
+                               const void* d_saved, size_t saved_bytes, const float* d_g_rgb_c, void* d_workspace, size_t workspace_bytes,
+                               float* const* d_grads, float* d_g_rows, int32_t ld_g_rows, void* stream);
+
 /* ---- the decoder on plain f16 MFMA with half-precision activations (ABI v7, added) ---------- */
 /* The same network (bundle_size 2, feat_dim 16, voxel_dim 8, num_layers 1 .. 16) under a narrower, explicit contract: weights f16(w)
  * (the up stage folded with out_conv in fp64, then rounded once), biases fp32; the 27 input channels read in place from the fp32 rows
